@@ -31,15 +31,25 @@ value = algorithmic bytes of all mixes on all ranks / max-over-ranks wall time, 
 algorithmic bytes = (K + 2) * P * 4 per device mix (K neighbour reads + local read + output
 write). Inputs are resident in HBM when the timed region starts.
 
-Launch: ``python bench.py [--gpus N --steps K --warmup W]``. With N > 1 and no RANK/WORLD_SIZE in
+A plain run (``python bench.py --gpus N --steps K --warmup W``) does what the headline needs and no
+more: it sets up, warms up, times exactly K rounds, writes ``--dump-outputs DIR`` if asked and
+prints the line; ``ms_per_step`` is the wall time of one timed round. Everything else the line can
+hold is measured only with ``--full``: the scattered-order rounds, the placement-calibrated leg,
+the CPU baselines, the live PMC traffic passes and the e2e leg at N = 1; the halo check, the
+decomposition and the other partitions' legs at N > 1. ``--dump-outputs DIR`` writes a seeded
+sample and whole-row fp64 sums of the stack the last timed round wrote (``dump_outputs``); the
+inputs are seeded per device, so the same arguments give the same files on every run and build.
+
+Launch: ``python bench.py [--gpus N --steps K --warmup W] [--full]``. With N > 1 and no RANK/WORLD_SIZE in
 the environment the bench launches its own ranks: ``python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1`` as a child process, before anything touches the GPU;
 the parent relays rank 0's JSON line and exits with the run's status. Under an external
 torch.distributed.run it runs as the rank it is given.
 
 Time: ``--total-seconds`` (default 420) bounds the whole run from the first launch: the headline
-is always measured; the extra legs, the CPU baselines, the PMC passes and the e2e leg each run
-only if the budget left covers their estimate, otherwise they are listed as ``skipped: budget``.
+is always measured; with ``--full`` the extra legs, the CPU baselines, the PMC passes and the e2e
+leg each run only if the budget left covers their estimate, otherwise they are listed as
+``skipped: budget``.
 
 Exit status: 0 = the line is complete; 3 = the transport the headline needs (RCCL) could not be
 opened on every rank, or the exchanging headline raised on every rank (the line is printed with
@@ -70,6 +80,15 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline, measure and check everything else the line can hold: the "
+                        "scattered-order rounds, the placement-calibrated leg, the CPU baselines, the live PMC "
+                        "traffic passes and the e2e leg (N = 1); the halo check, the decomposition and the other "
+                        "partitions' legs (N > 1). Without it the run sets up, warms up, times --steps rounds "
+                        "and prints the line")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed rounds, write what the last one computed (the shard's mixed stack) as "
+                        "float32 / float64 DIR/<name>.npy files (dump_outputs)")
     p.add_argument("--params", type=int, default=25_000_000, help="P, fp32 params per bucket")
     p.add_argument("--neighbours", type=int, default=8, help="K (even: ring window K/2 per side)")
     p.add_argument("--devices", type=int, default=128,
@@ -744,6 +763,53 @@ def run_leg(args, shard, world, steps, warmup, timed_kernel=True):
     return elapsed, durations, launches
 
 
+DUMP_BUDGET_BYTES = 48 * 2**20  # --dump-outputs: every rank's sample and column files together (< 64 MB with the sums)
+DUMP_EDGE = 4096                # columns kept whole at each end of a row (a kernel's head and tail paths)
+DUMP_SEED = 20261015
+
+
+def dump_columns(P: int, rows: int, budget: int = DUMP_BUDGET_BYTES):
+    """The columns of a ``[rows, P]`` fp32 stack that ``--dump-outputs`` keeps within ``budget``
+    bytes (a kept column costs 4 bytes in every row of the sample and 8 in the column file): all
+    of them when that fits, else the first and last ``DUMP_EDGE`` of a row and a seeded sample of
+    the columns between (sorted, the same for the same P, rows and budget)."""
+    import numpy as np
+    per_row = max(1, int(budget) // (4 * max(1, rows) + 8))
+    if P <= per_row:
+        return np.arange(P, dtype=np.int64)
+    edge = min(DUMP_EDGE, per_row // 4)
+    rng = np.random.default_rng(DUMP_SEED)
+    mid = np.unique(rng.integers(edge, P - edge, size=per_row - 2 * edge, dtype=np.int64))
+    return np.concatenate([np.arange(edge, dtype=np.int64), mid, np.arange(P - edge, P, dtype=np.int64)])
+
+
+def dump_outputs(path: str, shard, rank: int = 0, world: int = 1) -> dict:
+    """``--dump-outputs``: what the timed rounds left in the shard's ``mixed`` stack (row i = the mix
+    of local device i, what a caller of ``round`` reads), written after the last timed round:
+    ``mixed_sample.npy`` (fp32 ``[L, C]``: the ``dump_columns`` of every row), ``mixed_columns.npy``
+    (fp64 ``[C]``: their column numbers) and ``mixed_row_sums.npy`` (fp64 ``[L]``: every row summed
+    whole in fp64, so an element outside the sample still shows). At N > 1 each rank writes its own
+    rows as ``<name>_rank<r>.npy`` within a 1/N share of ``DUMP_BUDGET_BYTES``, so the directory
+    stays under 64 MB at every N. Returns {file: bytes}."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    mixed = shard.mixed
+    cols = dump_columns(int(mixed.shape[1]), int(mixed.shape[0]), DUMP_BUDGET_BYTES // max(1, world))
+    idx = torch.from_numpy(cols).to(mixed.device)
+    sample = torch.stack([row.index_select(0, idx) for row in mixed]).cpu().numpy()
+    sums = torch.stack([row.sum(dtype=torch.float64) for row in mixed]).cpu().numpy()
+    suffix = f"_rank{rank}" if world > 1 else ""
+    written = {}
+    for name, arr in (("mixed_sample", sample.astype(np.float32, copy=False)),
+                      ("mixed_columns", cols.astype(np.float64)), ("mixed_row_sums", sums.astype(np.float64))):
+        file = os.path.join(path, f"{name}{suffix}.npy")
+        np.save(file, arr)
+        written[os.path.basename(file)] = os.path.getsize(file)
+    return written
+
+
 INFINITY_CACHE_BYTES = 256 * 2**20  # MI355X_MICROARCH.md: Infinity Cache (L3) 256 MiB
 
 
@@ -895,7 +961,9 @@ def decompose_round(shard, world: int, steps: int, warmup: int, head_avg_ms: flo
     groups = []
     for g in range(G):
         busiest = max(plan.group_link_elems(g, lane=False).values(), default=0) * 4
+        lane_g = sum(m.count for m in plan.groups[g] if m.lane) * 4  # the group's host-lane bytes, all ranks
         groups.append({"ms": round(group_ms[g], 4), "busiest_link_MB": round(busiest / 1e6, 2),
+                       "lane_MB": round(lane_g / 1e6, 2),
                        "link_GBps": round(busiest / (group_ms[g] * 1e-3) / 1e9, 2) if group_ms[g] > 0 else None,
                        "predicted_ms": round(pred[g], 4) if pred[g] is not None else None})
     crit = sum(max(plan.group_link_elems(g, lane=False).values(), default=0) for g in range(G)) * 4
@@ -1288,11 +1356,15 @@ def main():
             headline, headline_exchanges = "params", False
             res = measure_headline("params")
         shard, info, autotune, elapsed, durations, launches_per_step = res
-    # N > 1: the halo the timed rounds delivered, row by row against the rows their owners hold
-    # (exact 32-bit-pattern checksums), so the line proves the exchange moved the right bytes over
-    # RCCL, the relays and the host lane on this node
+    dumped = None
+    if args.dump_outputs:  # the last timed round's results, before any other leg runs on the shard
+        watchdog.enter("dump outputs")
+        dumped = dump_outputs(args.dump_outputs, shard, rank, world)
+    # N > 1 (--full): the halo the timed rounds delivered, row by row against the rows their owners
+    # hold (exact 32-bit-pattern checksums), so the line proves the exchange moved the right bytes
+    # over RCCL, the relays and the host lane on this node
     halo_check = None
-    if world > 1 and info.get("route") is not None:
+    if args.full and world > 1 and info.get("route") is not None:
         watchdog.enter("halo check")
 
         def gather(obj):
@@ -1317,7 +1389,7 @@ def main():
     route = info.get("route")
     reuse = window_fits_cache(shard_P(info, P), K)
     scat = None
-    if reuse and not args.window_batch and len(interior) > 1:
+    if args.full and reuse and not args.window_batch and len(interior) > 1:
         watchdog.enter("timed rounds, scattered order")
         scat = timed_scattered(shard, args.steps)
     t_headline = time.perf_counter() - t_head0
@@ -1391,6 +1463,8 @@ def main():
                               "algorithmic bytes, value_scattered is the same round with no two consecutive mixes "
                               "sharing a row (DESIGN.md §5)") if reuse else None,
                 "budget": {"total_s": args.total_seconds, "headline_s": round(t_headline, 1)},
+                "full": args.full,
+                "dumped_outputs": dumped,
             },
             "roofline": {
                 "bound": "hbm",
@@ -1439,7 +1513,7 @@ def main():
 
     # what the report still needs after the legs: rank 0's PMC passes (a child process each) and,
     # at N = 1, the CPU baselines and the e2e leg
-    live = not args.no_live_traffic and not args.window_batch
+    live = args.full and not args.no_live_traffic and not args.window_batch
     pmc_est = 45.0
     reserve = 15.0 + (2 * pmc_est if live else 0.0)
     legs = {}
@@ -1479,7 +1553,7 @@ def main():
     # N = 1: the same rounds on placement-calibrated stacks (placement.calibrated_stacks: the fastest
     # of --placement-leg allocations per stack), beside the plain-allocation headline; the headline's
     # stacks are released first and the leg's candidates go back to the driver after it
-    if world == 1 and args.placement_leg > 1 and args.placement_candidates <= 1:
+    if args.full and world == 1 and args.placement_leg > 1 and args.placement_candidates <= 1:
         est = 2.5 * t_headline + 30.0
         if budget.left() - reserve - 45.0 >= est:
             watchdog.enter("placement-calibrated leg")
@@ -1510,7 +1584,7 @@ def main():
     # only, the model's prediction), so a scaling result explains itself. Budget-gated (the
     # headline never is) and run as a leg with its own watchdog budget: if it hangs in a
     # collective, rank 0 prints the line with the headline and the decomposition's error.
-    if world > 1 and headline_exchanges and route is not None and not args.no_decomposition:
+    if args.full and world > 1 and headline_exchanges and route is not None and not args.no_decomposition:
         dsteps = args.decomp_steps or min(args.steps, 10)
         est = decomposition_estimate(elapsed / args.steps, dsteps, args.warmup)
         if agree_all(budget.left() - reserve >= est):
@@ -1540,7 +1614,7 @@ def main():
             result["decomposition"] = decomp
             result["config"]["halo_route"]["achieved_critical_ms"] = decomp.get("exchange_groups_ms_sum")
 
-    if world > 1 and not args.no_extra_legs and not weak:
+    if args.full and world > 1 and not args.no_extra_legs and not weak:
         shard.close()
         del shard
         drop_cached()
@@ -1641,15 +1715,15 @@ def main():
             result.pop("partitions", None)
     if world > 1:
         dist.barrier()
-    # CPU baselines: rank 0, N = 1 only (bounded samples), each only if the budget left covers it
+    # CPU baselines (--full): rank 0, N = 1 only (bounded samples), each only if the budget left covers it
     watchdog.enter("baselines and report")
     skipped = []
     if rank == 0:
-        e2e = args.e2e and world == 1
+        e2e = args.full and args.e2e and world == 1
         e2e_est = 30.0 if e2e else 0.0
         tail = e2e_est + (2 * pmc_est if live else 0.0)
         result["cpu_baseline"] = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if budget.allows(args.cpu_seconds + 10 + tail):
                 result["cpu_baseline"] = cpu_baseline(P, K, args.cpu_seconds)
             else:

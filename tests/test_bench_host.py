@@ -241,6 +241,75 @@ def test_bench_defaults_put_the_devices_partition_in_the_headline(monkeypatch):
     assert a.partition == "devices" and a.total_seconds == 420.0 and a.watchdog_seconds is None
 
 
+def test_full_and_dump_outputs_are_opt_in(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "somewhere"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "somewhere"
+
+
+def test_dump_columns_samples_a_large_stack_within_its_budget():
+    """A stack over the budget keeps both ends of every row and a seeded sample between, the same
+    on every call; 128 rows of 25M stay under 64 MB with the column and row-sum files; a stack
+    within the budget is kept whole."""
+    import numpy as np
+    import bench
+    P = 25_000_000
+    cols = bench.dump_columns(P, 128)
+    assert cols.dtype == np.int64 and np.array_equal(cols, bench.dump_columns(P, 128))
+    assert np.all(np.diff(cols) > 0) and cols[0] == 0 and cols[-1] == P - 1
+    assert np.array_equal(cols[:bench.DUMP_EDGE], np.arange(bench.DUMP_EDGE))
+    assert np.array_equal(cols[-bench.DUMP_EDGE:], np.arange(P - bench.DUMP_EDGE, P))
+    assert 90_000 < len(cols) <= bench.DUMP_BUDGET_BYTES // 4 // 128
+    assert 128 * len(cols) * 4 + len(cols) * 8 + 128 * 8 + 3 * 128 <= 64 * 2**20
+    assert np.array_equal(bench.dump_columns(100_003, 12), np.arange(100_003))
+    # more rows than the budget has columns for: still in bounds, still sorted
+    few = bench.dump_columns(P, 4096)
+    assert 0 < len(few) <= bench.DUMP_BUDGET_BYTES // 4 // 4096 and few[0] == 0 and few[-1] == P - 1
+    assert np.all(np.diff(few) > 0)
+    # N > 1: every rank samples within a 1/N share, so all ranks' files together keep the limit:
+    # 8 ranks of 16 rows (the default population), and of 4 rows (the fewest a K = 8 window allows,
+    # where the column files weigh most)
+    for world, rows in ((2, 64), (8, 16), (8, 4), (8, 128)):
+        c = bench.dump_columns(P, rows, bench.DUMP_BUDGET_BYTES // world)
+        assert c[0] == 0 and c[-1] == P - 1 and np.all(np.diff(c) > 0)
+        total = world * (rows * len(c) * 4 + len(c) * 8 + rows * 8 + 3 * 128)
+        assert total <= 64 * 10**6, (world, rows, total)
+        assert total >= 0.7 * bench.DUMP_BUDGET_BYTES, (world, rows, total)  # and the budget is used
+
+
+@pytest.mark.parametrize("world", [1, 2, 8])
+def test_dump_outputs_of_all_ranks_stay_within_the_limit(tmp_path, monkeypatch, world):
+    """dump_outputs itself, on a scaled-down budget (48 KiB for 48 MiB) and CPU stacks: the files of
+    all ranks together stay within 64/48 of the budget on the sampled path, hold fp32 / fp64 only,
+    and the sample and sums are the stack's own values."""
+    import types
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 48 * 2**10)
+    monkeypatch.setattr(bench, "DUMP_EDGE", 16)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    rows, P = 128 // world, 20_011
+    total = 0
+    for rank in range(world):
+        mixed = torch.arange(rows * P, dtype=torch.float32).reshape(rows, P) * 0.5 + rank
+        written = bench.dump_outputs(str(tmp_path), types.SimpleNamespace(mixed=mixed), rank, world)
+        sfx = f"_rank{rank}" if world > 1 else ""
+        assert sorted(written) == [f"mixed_columns{sfx}.npy", f"mixed_row_sums{sfx}.npy", f"mixed_sample{sfx}.npy"]
+        sample, cols, sums = (np.load(tmp_path / f"mixed_{n}{sfx}.npy") for n in ("sample", "columns", "row_sums"))
+        assert sample.dtype == np.float32 and cols.dtype == np.float64 and sums.dtype == np.float64
+        assert len(cols) < P and sample.shape == (rows, len(cols))  # the sampled path
+        assert np.array_equal(sample, mixed.numpy()[:, cols.astype(np.int64)])
+        assert np.array_equal(sums, mixed.numpy().astype(np.float64).sum(axis=1))
+        total += sum(written.values())
+    assert total == sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path))
+    assert total <= 64 * 2**10, (world, total)
+
+
 def test_record_status_first_writer_wins(tmp_path, monkeypatch):
     import bench
     path = tmp_path / "st"

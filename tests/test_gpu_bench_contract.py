@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_line_contract():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--params", "1000000", "--devices", "16", "--steps", "3",
-           "--warmup", "1", "--cpu-seconds", "0.5", "--cpu-pool-seconds", "0", "--no-live-traffic"]
+           "--warmup", "1", "--full", "--cpu-seconds", "0.5", "--cpu-pool-seconds", "0", "--no-live-traffic"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=110, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -42,6 +42,55 @@ def test_bench_line_contract():
     assert leg["value"] > 0 and 0 < leg["frac"] < 1 and leg["placement"]["candidates"] >= 1
 
 
+def test_plain_run_times_the_steps_only_and_dumps_the_last_rounds_outputs(tmp_path):
+    """Without --full the run is the headline alone (no CPU baseline, no legs, no e2e), --steps is
+    the number of timed rounds, and --dump-outputs writes the stack the last round computed: every
+    row equal to the oracle's sequential mix of the seeded inputs, bit for bit, in the sampled
+    columns, and its fp64 sum over the whole row."""
+    import numpy as np
+    import torch
+    from federated_amd.population import RingShardPlan
+    from oracle.cfa_oracle import sequential_mix
+
+    P, D, K = 100_003, 12, 8  # an odd row length, whole rows within the dump's budget
+    out = str(tmp_path / "dump")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--params", str(P), "--devices", str(D),
+           "--steps", "3", "--warmup", "1", "--dump-outputs", out]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=110, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["exit_status"] == 0
+    assert d["unit"] == "GB/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["metric"] == "device-resident GB/s, CFA reduce of K neighbour fp32 param buckets; 1/2/4/8 GPU"
+    assert d["ms_per_step"] > 0
+    assert abs(d["value"] - D * (K + 2) * P * 4 / (d["ms_per_step"] * 1e-3) / 1e9) <= 0.01 * d["value"]
+    assert d["config"]["full"] is False and d["cpu_baseline"] is None
+    for key in ("legs", "e2e", "cpu_baseline_pool", "value_scattered", "decomposition", "partitions"):
+        assert key not in d, key
+    assert d["config"]["budget"]["skipped"] == [] and "traffic_source" not in d["roofline"]
+
+    files = sorted(os.listdir(out))
+    assert files == ["mixed_columns.npy", "mixed_row_sums.npy", "mixed_sample.npy"]
+    assert d["config"]["dumped_outputs"] == {f: os.path.getsize(os.path.join(out, f)) for f in files}
+    assert sum(d["config"]["dumped_outputs"].values()) <= 64 * 2**20
+    sample, cols, sums = (np.load(os.path.join(out, f"mixed_{n}.npy")) for n in ("sample", "columns", "row_sums"))
+    assert sample.dtype == np.float32 and cols.dtype == np.float64 and sums.dtype == np.float64
+    assert np.array_equal(cols, np.arange(P)) and sample.shape == (D, P) and sums.shape == (D,)
+    # the inputs as bench.seed_shard draws them: device g's bucket from seed 20261015 + g
+    gen = torch.Generator(device="cuda:0")
+    models = []
+    for g in range(D):
+        gen.manual_seed(20261015 + g)
+        models.append(torch.empty(P, dtype=torch.float32, device="cuda:0").normal_(generator=gen).cpu().numpy())
+    plan = RingShardPlan(0, 1, D, K // 2)
+    for g in range(D):
+        ref = sequential_mix(models[g], [models[j] for j in plan.neighbours(g)], [1.0 / (K + 1)] * K)
+        assert np.array_equal(sample[g], ref), g
+        assert abs(sums[g] - ref.astype(np.float64).sum()) <= 1e-9 * np.abs(ref).astype(np.float64).sum(), g
+
+
 N_GT_1_FIELDS = [("value", float), ("ms_per_step", float), ("n_gpus", int), ("exit_status", int),
                  ("config", dict), ("roofline", dict), ("partitions", dict)]
 CONFIG_FIELDS = ["partition", "transport", "comparable", "rccl_version", "halo_route", "cache_reuse", "rows_note",
@@ -53,7 +102,7 @@ def _self_launched(extra, timeout=240):
     """python3 bench.py --gpus 2 ... with no torch.distributed.run: bench launches its own ranks
     (on a one-GPU box both share the card)."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--params", "1000000", "--steps", "3",
-           "--warmup", "1", "--no-live-traffic", "--total-seconds", "200"] + extra
+           "--warmup", "1", "--full", "--no-live-traffic", "--total-seconds", "200"] + extra
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=env)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -82,7 +131,8 @@ def test_self_launched_n2_line_matches_the_documented_schema():
     assert links["rates_GBps"][0][1] > 0 and links["rates_GBps"][1][0] > 0 and links["rates_GBps"][0][0] is None
     at = c["halo_route"]["autotune"]
     assert at["mode"] == "links" and at["predicted_ms"] > 0
-    assert at["plan"].split("+")[0] in ("uniform", "measured", "direct")
+    # "<cost model>[/<parts per row>][+lane]" (halo.choose_route's candidate names)
+    assert at["plan"].split("+")[0].split("/")[0] in ("uniform", "measured", "direct")
     assert at["candidates_predicted_ms"]["uniform"] > 0 and c["halo_route"]["link_cost"] in ("uniform", "measured")
     # round 6: the ranks run at whatever hardware-queue count the box exports (no override): the
     # lane's waits are on the host, and every stream comes from the rank's stream budget
@@ -107,7 +157,14 @@ def test_self_launched_n2_line_matches_the_documented_schema():
         assert key in dc, key
     assert dc["exchange_only_ms"] > 0 and dc["compute_only_ms"] > 0 and dc["t_mix_ms"] > 0
     assert len(dc["exchange_groups"]) == c["halo_route"]["groups"]
-    assert all(g["ms"] >= 0 and g["busiest_link_MB"] > 0 for g in dc["exchange_groups"])
+    # busiest_link_MB counts the transport's links alone: where the host-staged gloo link probes far
+    # slower than the host lane, halo.choose_route puts a whole group on the lane: a group may show
+    # no link bytes only if it carries lane bytes itself, and only a +lane plan has any
+    for g in dc["exchange_groups"]:
+        assert g["ms"] >= 0 and g["busiest_link_MB"] >= 0 and g["lane_MB"] >= 0
+        assert g["busiest_link_MB"] > 0 or g["lane_MB"] > 0, (at["plan"], dc["exchange_groups"])
+        assert g["lane_MB"] == 0 or at["plan"].endswith("+lane"), (at["plan"], dc["exchange_groups"])
+    assert abs(sum(g["lane_MB"] for g in dc["exchange_groups"]) - (c["halo_route"]["lane_MB"] or 0)) <= 0.1
     assert c["halo_route"]["achieved_critical_ms"] == dc["exchange_groups_ms_sum"]
     assert dc["achieved_ms"] == d["ms_per_step"]
     assert set(c["budget"]) >= {"total_s", "headline_s", "left_s", "skipped"}
@@ -117,6 +174,38 @@ def test_self_launched_n2_line_matches_the_documented_schema():
     p = d["partitions"]["params"]
     assert p["cache_reuse"] is True and p["value"] > 0 and p["value_scattered"] > 0
     assert "weak" in d["partitions"]
+
+
+def test_self_launched_plain_n2_run_is_the_headline_alone_and_its_dump_keeps_the_limit(tmp_path):
+    """Without --full the N = 2 line holds the headline and what it needs (transport, link and lane
+    probes, the route) but no halo check, decomposition or partitions; --dump-outputs gives each
+    rank's rows as <name>_rank<r>.npy on the sampled path, all files together under 64 MB."""
+    import numpy as np
+    out = str(tmp_path / "dump")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--params", "1000000", "--steps", "3",
+           "--warmup", "1", "--transport", "torch", "--total-seconds", "200", "--dump-outputs", out]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT, env=env)
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
+    d = json.loads(lines[0])
+    c = d["config"]
+    assert d["n_gpus"] == 2 and d["steps"] == 3 and d["exit_status"] == 0 and d["ms_per_step"] > 0
+    assert c["full"] is False and c["partition"] == "devices" and c["headline_fallback"] is None
+    assert c["links"]["rates_GBps"][0][1] > 0 and c["halo_route"]["autotune"]["mode"] == "links"
+    assert c["halo_check"] is None and c["halo_route"]["achieved_critical_ms"] is None
+    for key in ("decomposition", "partitions", "value_scattered", "cpu_baseline_pool", "e2e", "legs"):
+        assert key not in d, key
+    files = sorted(os.listdir(out))
+    assert files == sorted(f"mixed_{n}_rank{k}.npy" for n in ("columns", "row_sums", "sample") for k in (0, 1))
+    assert sum(os.path.getsize(os.path.join(out, f)) for f in files) <= 64 * 10**6
+    for k in (0, 1):
+        sample, cols, sums = (np.load(os.path.join(out, f"mixed_{n}_rank{k}.npy"))
+                              for n in ("sample", "columns", "row_sums"))
+        assert sample.dtype == np.float32 and cols.dtype == np.float64 and sums.dtype == np.float64
+        assert sample.shape == (64, len(cols)) and len(cols) < 1_000_000 and sums.shape == (64,)
+        assert np.all(np.isfinite(sample)) and np.all(sums != 0)
+    assert c["dumped_outputs"] == {f: os.path.getsize(os.path.join(out, f)) for f in files if f.endswith("_rank0.npy")}
 
 
 def test_self_launched_n2_rccl_refused_falls_back_and_exits_3():

@@ -7,7 +7,7 @@
 #   tests      python -m pytest tests -m gpu -x (the driver's round-end command, with per-test timeouts)
 #   tests:EXPR the same restricted by -k EXPR
 #   smoke      __graft_entry__.smoke()
-#   bench      the default bench line (CPU baselines, live PMC traffic)
+#   bench      the whole bench line (bench.py --full: CPU baselines, live PMC traffic, the legs)
 #   rocprof    rocprofv3 --kernel-trace --stats of the bench command -> gpurun_out/prof_TAG/
 #   fetch      rocprofv3 --pmc FETCH_SIZE of the bench command     -> gpurun_out/pmc_TAG/
 #   write      rocprofv3 --pmc WRITE_SIZE of the bench command     -> gpurun_out/pmc_TAG/
@@ -87,7 +87,7 @@ for s in "$@"; do
     tests) step pytest_gpu 1100 python -u -m pytest -x -v --timeout 200 --timeout-method thread tests -m gpu -p no:cacheprovider ;;
     tests:*) step pytest_sel 600 python -u -m pytest -x -v --timeout 200 --timeout-method thread tests -m gpu -p no:cacheprovider -k "${s#tests:}" ;;
     smoke) step smoke 200 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench 500 python bench.py --steps 20 --warmup 5 ;;
+    bench) step bench 500 python bench.py --steps 20 --warmup 5 --full ;;
     rocprof) step rocprof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_$TAG" -o run --output-format csv -- python3 $BENCH ;;
     fetch) step fetch 300 rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc_$TAG" -o fetch --output-format csv -- python3 $BENCH ;;
     write) step write 300 rocprofv3 --pmc WRITE_SIZE -d "$OUT/pmc_$TAG" -o write --output-format csv -- python3 $BENCH ;;

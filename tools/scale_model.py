@@ -16,7 +16,7 @@ those rates and C_halo / B_link becomes its predicted exchange time (for lane 0 
 Pure host arithmetic (no GPU). Usage: python tools/scale_model.py [--params P] [--devices D]
 
 With ``--from-lines FILE`` (bench JSON lines, one per N, e.g. the driver's SCALE record or the
-lines of `python bench.py --gpus N`), the model is re-evaluated with what each N > 1 line
+lines of `python bench.py --gpus N --full`), the model is re-evaluated with what each N > 1 line
 MEASURED instead of the assumptions: B_link = the line's `config.links.median_GBps`, delta and
 t_mix from its `decomposition`, T(1) from the N = 1 line's `ms_per_step`; each row prints the
 model's speed-up next to the achieved one (value / value at N = 1)."""
