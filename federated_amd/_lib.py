@@ -100,6 +100,8 @@ SIGNATURES = {
     "cfa_mix_window_f32": (_c_int, [_PP, _PP, _c_float_p, _c_int, _c_int, _c_int, _c_size_t, _c_void_p]),
     "cfa_mix_ring_round_f32": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_int, _c_int, _c_int,
                                         _c_size_t, _c_void_p]),
+    "cfa_mix_ring_slide_f32": (_c_int, [_c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_void_p, _c_int, _c_int,
+                                        _c_int, _c_int, _c_int, _c_size_t, _c_void_p]),
     "cfa_mix_population_tf1_f32": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int,
                                             _c_size_t, _c_int, _c_size_t, _c_size_t, _c_void_p, _c_void_p]),
     "cfa_mix_population_f32": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,

@@ -1,6 +1,7 @@
 // cfa_population.hip — whole-population rounds: the CSR one-launch kernel
 // (cfa_mix_population_f32) and the sliding-window passes (cfa_mix_window_f32) that load each
-// row of a ring window once for up to 8 consecutive devices.
+// row of a ring window once for up to 8 consecutive devices, and the sliding ring round
+// (cfa_mix_ring_slide_f32) that reads every row of a run of ring devices once.
 #include "cfa_internal.h"
 
 // Resident workgroups per CU across a whole population launch (all devices together). 8 by
@@ -269,6 +270,95 @@ __global__ __launch_bounds__(kBlock) void ring_round_kernel(RingArgs ra, long lo
   window_body<HL, HR, U, SC1>(w, nvec);
 }
 
+// ------------------------------------------------------------------------------------------
+// Sliding ring round (cfa_mix_ring_slide_f32): every row of a run of consecutive ring devices is
+// read ONCE and every output written once. A workgroup owns a column tile of kBlock float4 and a
+// segment (blockIdx.y) of `seg` consecutive devices. It walks the segment's row stream
+// (rows d0-HL .. d0+len-1+HR, mod `rows`) through a ring of W + PF register slots, W = HL+HR+1:
+// device m of the segment folds stream rows m .. m+W-1 (its local row is m+HL) while the loads of
+// rows m+W .. m+W-1+PF are in flight. The device loop is unrolled W + PF times, so stream row q
+// always sits in slot q mod (W + PF) and every register index is static. A segment re-reads HL+HR
+// halo rows: a call reads count + segments * (HL+HR) rows. The fold is window_fold's: local row,
+// rows below in ascending order, rows above, t = x - acc; t = a*t; acc = acc + t.
+// ------------------------------------------------------------------------------------------
+struct SlideArgs {
+  const float* in;
+  float* out;
+  const float* alphas;             // [count] device array, one coefficient per device of the run
+  long long in_pitch, out_pitch;   // floats between consecutive rows
+  long long off;                   // element offset of this launch's chunk
+  int rows, first, count, seg;     // seg: devices per segment
+};
+
+template <int HL, int HR, int PF, bool SC1>
+__global__ __launch_bounds__(kBlock) void ring_slide_kernel(SlideArgs sa, long long nvec) {
+  constexpr int W = HL + HR + 1;
+  constexpr int RS = W + PF;
+  const int n0 = (int)blockIdx.y * sa.seg;  // first device of the segment, relative to sa.first
+  const int len = min(sa.seg, sa.count - n0);
+  const int total = len + HL + HR;  // rows of the segment's stream
+  const int d0 = sa.first + n0;
+  int g0 = (d0 - HL) % sa.rows;
+  if (g0 < 0) g0 += sa.rows;
+  const int o0 = d0 >= sa.rows ? d0 - sa.rows : d0;
+  const float* const in = sa.in + sa.off;
+  float* const out = sa.out + sa.off;
+  const float* const in_end = in + (long long)sa.rows * sa.in_pitch;
+  float* const out_end = out + (long long)sa.rows * sa.out_pitch;
+  for (long long t = blockIdx.x; t * kBlock < nvec; t += gridDim.x) {
+    const long long i = t * kBlock + threadIdx.x;
+    if (i >= nvec) continue;
+    const unsigned voff = (unsigned)(i * 16);  // a chunk is at most kMaxChunkVec float4: below 2^31
+    const float* rp = in + (long long)g0 * sa.in_pitch;  // next row of the stream to load
+    float* op = out + (long long)o0 * sa.out_pitch;      // next output row
+    f4 r[RS];
+#pragma unroll
+    for (int q = 0; q < RS - 1; ++q)
+      if (q < total) {
+        r[q] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(reinterpret_cast<const char*>(rp) + voff));
+        rp += sa.in_pitch;
+        if (rp == in_end) rp = in;
+      }
+    for (int n = 0; n < len; n += RS) {
+#pragma unroll
+      for (int u = 0; u < RS; ++u) {
+        const int m = n + u;
+        if (m < len) {
+          if (m + RS - 1 < total) {  // stream row m+W-1+PF: into the slot row m-1 has left
+            r[(u + RS - 1) % RS] =
+                __builtin_nontemporal_load(reinterpret_cast<const f4*>(reinterpret_cast<const char*>(rp) + voff));
+            rp += sa.in_pitch;
+            if (rp == in_end) rp = in;
+          }
+          const float a = sa.alphas[n0 + m];
+          f4 acc = r[(u + HL) % RS];
+#pragma unroll
+          for (int j = 0; j < HL; ++j) {
+            f4 x = r[(u + j) % RS] - acc;
+            x = a * x;
+            acc = acc + x;
+          }
+#pragma unroll
+          for (int j = 0; j < HR; ++j) {
+            f4 x = r[(u + HL + 1 + j) % RS] - acc;
+            x = a * x;
+            acc = acc + x;
+          }
+          if constexpr (SC1) {
+            const __amdgpu_buffer_rsrc_t o =
+                __builtin_amdgcn_make_buffer_rsrc((void*)op, 0, (unsigned)(nvec * 16), 0x00020000);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, acc), o, (int)voff, 0, kStoreSc1);
+          } else {
+            __builtin_nontemporal_store(acc, reinterpret_cast<f4*>(reinterpret_cast<char*>(op) + voff));
+          }
+          op += sa.out_pitch;
+          if (op == out_end) op = out;
+        }
+      }
+    }
+  }
+}
+
 // Scalar window pass (misaligned rows, the < 4-element tail): runtime hl / hr.
 __global__ __launch_bounds__(kBlock) void window_scalar_kernel(WindowArgs w, int hl, int hr,
                                                                long long begin, long long P) {
@@ -367,6 +457,60 @@ const WindowLaunch kWindowLaunch[5][5] = {
     {CFA_W(3, 0), CFA_W(3, 1), CFA_W(3, 2), CFA_W(3, 3), CFA_W(3, 4)},
     {CFA_W(4, 0), CFA_W(4, 1), CFA_W(4, 2), CFA_W(4, 3), CFA_W(4, 4)}};
 #undef CFA_W
+
+// Launch shape of the sliding ring round. The environment overrides are read at each launch, so
+// one process can compare shapes on the same buffers (tools/probe/ring_slide.py); results are
+// identical for every shape.
+struct SlideTune {
+  int segments, wg_per_cu, pf, sc1;
+};
+static SlideTune slide_tune() {
+  SlideTune t{1, 4, 2, 0};  // tools/probe/ring_slide.py sweep, profiles/r07_ring_slide_sweep.jsonl
+  if (const char* e = getenv("CFA_SLIDE_SEGMENTS")) t.segments = atoi(e) > 0 ? atoi(e) : t.segments;
+  if (const char* e = getenv("CFA_SLIDE_WG_PER_CU")) t.wg_per_cu = atoi(e) > 0 ? atoi(e) : t.wg_per_cu;
+  if (const char* e = getenv("CFA_SLIDE_PF")) t.pf = atoi(e) >= 1 && atoi(e) <= 4 ? atoi(e) : t.pf;
+  if (const char* e = getenv("CFA_SLIDE_SC1")) t.sc1 = atoi(e) ? 1 : 0;
+  return t;
+}
+template <int HL, int HR, int PF>
+void launch_slide_pf(const SlideArgs& c, long long m, dim3 grid, bool sc1, hipStream_t st) {
+  if (sc1) ring_slide_kernel<HL, HR, PF, true><<<grid, kBlock, 0, st>>>(c, m);
+  else ring_slide_kernel<HL, HR, PF, false><<<grid, kBlock, 0, st>>>(c, m);
+}
+template <int HL, int HR>
+void launch_ring_slide(const SlideArgs& sa, long long nvec, hipStream_t st) {
+  const SlideTune t = slide_tune();
+  int segments = t.segments < sa.count ? t.segments : sa.count;
+  if (segments > 65535) segments = 65535;
+  SlideArgs c = sa;
+  c.seg = (sa.count + segments - 1) / segments;
+  const unsigned gy = (unsigned)((sa.count + c.seg - 1) / c.seg);  // no empty segment
+  for (long long done = 0; done < nvec; done += kMaxChunkVec) {
+    const long long m = (nvec - done) < kMaxChunkVec ? (nvec - done) : kMaxChunkVec;
+    c.off = done * 4;
+    const long long tiles = (m + kBlock - 1) / kBlock;
+    // the launch's workgroups over all segments: about wg_per_cu per CU in all
+    long long gx = ((long long)device_cus() * t.wg_per_cu + gy - 1) / gy;
+    if (gx > tiles) gx = tiles;
+    if (gx < 1) gx = 1;
+    const dim3 grid((unsigned)gx, gy);
+    switch (t.pf) {
+      case 1: launch_slide_pf<HL, HR, 1>(c, m, grid, t.sc1, st); break;
+      case 3: launch_slide_pf<HL, HR, 3>(c, m, grid, t.sc1, st); break;
+      case 4: launch_slide_pf<HL, HR, 4>(c, m, grid, t.sc1, st); break;
+      default: launch_slide_pf<HL, HR, 2>(c, m, grid, t.sc1, st); break;
+    }
+  }
+}
+using SlideLaunch = void (*)(const SlideArgs&, long long, hipStream_t);
+#define CFA_S(L, R) &launch_ring_slide<L, R>
+const SlideLaunch kSlideLaunch[5][5] = {
+    {CFA_S(0, 0), CFA_S(0, 1), CFA_S(0, 2), CFA_S(0, 3), CFA_S(0, 4)},
+    {CFA_S(1, 0), CFA_S(1, 1), CFA_S(1, 2), CFA_S(1, 3), CFA_S(1, 4)},
+    {CFA_S(2, 0), CFA_S(2, 1), CFA_S(2, 2), CFA_S(2, 3), CFA_S(2, 4)},
+    {CFA_S(3, 0), CFA_S(3, 1), CFA_S(3, 2), CFA_S(3, 3), CFA_S(3, 4)},
+    {CFA_S(4, 0), CFA_S(4, 1), CFA_S(4, 2), CFA_S(4, 3), CFA_S(4, 4)}};
+#undef CFA_S
 }  // namespace
 
 extern "C" int cfa_mix_window_f32(float* const* out, const float* const* rows, const float* alphas,
@@ -423,6 +567,29 @@ extern "C" int cfa_mix_ring_round_f32(float* out, const float* in, size_t pitch,
   RingArgs ra{in, out, alphas, (long long)pitch, 0, D};
   kRingLaunch[hl][hr](ra, (long long)(P / 4), (hipStream_t)stream);
   return check_launch("ring_round");
+}
+
+extern "C" int cfa_mix_ring_slide_f32(float* out, size_t out_pitch, const float* in, size_t in_pitch,
+                                      const float* alphas, int rows, int first, int count, int hl, int hr,
+                                      size_t P, void* stream) {
+  if (!out || !in || !alphas) return fail(CFA_E_INVALID, "null buffer");
+  if (rows < 1 || count < 1) return fail(CFA_E_INVALID, "rows %d / count %d below 1", rows, count);
+  if (first < 0 || first >= rows || count > rows || (count != rows && first > rows - count))
+    return fail(CFA_E_INVALID, "devices %d..%d outside a ring of %d rows", first, first + count - 1, rows);
+  if (hl < 0 || hr < 0 || hl > 4 || hr > 4) return fail(CFA_E_INVALID, "window %d/%d outside 0..4", hl, hr);
+  if (hl + hr >= rows) return fail(CFA_E_INVALID, "window %d/%d wider than %d rows", hl, hr, rows);
+  if (in_pitch < P || out_pitch < P)
+    return fail(CFA_E_INVALID, "pitch %zu/%zu below P %zu", out_pitch, in_pitch, P);
+  if (P == 0) return CFA_OK;
+  const unsigned long long outb = addr(out), inb = addr(in);
+  const unsigned long long out_span = ((unsigned long long)(rows - 1) * out_pitch + P) * 4;
+  const unsigned long long in_span = ((unsigned long long)(rows - 1) * in_pitch + P) * 4;
+  if (outb < inb + in_span && inb < outb + out_span) return fail(CFA_E_INVALID, "out overlaps in");
+  if ((outb & 15) || (inb & 15) || (out_pitch % 4) || (in_pitch % 4) || (P % 4))
+    return fail(CFA_E_UNSUPPORTED, "ring slide needs 16-byte aligned rows (pitches and P multiples of 4)");
+  SlideArgs sa{in, out, alphas, (long long)in_pitch, (long long)out_pitch, 0, rows, first, count, count};
+  kSlideLaunch[hl][hr](sa, (long long)(P / 4), (hipStream_t)stream);
+  return check_launch("ring_slide");
 }
 
 extern "C" int cfa_mix_population_tf1_f32(float* const* out_ptrs, const float* const* src_ptrs,

@@ -537,6 +537,30 @@ class Engine:
                   int(hr), P, self.stream_handle(stream))
         return out
 
+    def ring_slide(self, out: torch.Tensor, models: torch.Tensor, alphas: torch.Tensor, first: int, count: int,
+                   hl: int, hr: int, stream=None) -> torch.Tensor:
+        """cfa_mix_ring_slide_f32: devices first .. first+count-1 of a stacked [rows, P] population,
+        each mixed with its ring window [d-hl .. d-1, d+1 .. d+hr] (mod rows), every row read once
+        and every output row written once. ``out`` and ``models`` are [rows, P] fp32 CUDA with unit
+        element stride (their row pitches may differ); ``alphas`` [count] fp32 CUDA, one coefficient
+        per device of the run; rows of ``out`` outside the run are left as they are. The library
+        validates the run and the layout (CFAError: CFA_E_INVALID / CFA_E_UNSUPPORTED)."""
+        for name, t in (("out", out), ("models", models)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 \
+                    or (t.shape[1] > 1 and t.stride(1) != 1):
+                raise TypeError(f"{name} must be a 2-D fp32 CUDA tensor with unit element stride")
+        rows, P = int(models.shape[0]), int(models.shape[1])
+        if tuple(out.shape) != (rows, P):
+            raise TypeError("out must have the shape of models")
+        if not alphas.is_cuda or alphas.dtype != torch.float32 or alphas.numel() < max(int(count), 1) \
+                or not alphas.is_contiguous():
+            raise TypeError("alphas must be a contiguous fp32 CUDA tensor of at least count entries")
+        out_pitch = int(out.stride(0)) if rows > 1 else P
+        in_pitch = int(models.stride(0)) if rows > 1 else P
+        _lib.call("cfa_mix_ring_slide_f32", out.data_ptr(), out_pitch, models.data_ptr(), in_pitch,
+                  alphas.data_ptr(), rows, int(first), int(count), int(hl), int(hr), P, self.stream_handle(stream))
+        return out
+
     def ge_population_step(self, out_ptrs: torch.Tensor, src_ptrs: torch.Tensor, state_ptrs: torch.Tensor,
                            grad_ptrs: torch.Tensor, csr_ptr: torch.Tensor, csr_idx: torch.Tensor,
                            csr_coef: torch.Tensor, D: int, rho: float, lr1: float, lr2: float, lr_split: int,

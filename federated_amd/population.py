@@ -139,6 +139,31 @@ def slice_bounds(P: int, parts: int, align: int = 64) -> List[int]:
 
 PARTITIONS = ("devices", "params", "hybrid")
 
+INFINITY_CACHE_BYTES = 256 * 2**20  # MI355X Infinity Cache (L3): the size gate of the fused round
+
+
+def window_exceeds_cache(P: int, K: int, itemsize: int = 4) -> bool:
+    """Is one mix's ring window ((K + 1) input rows of ``P`` elements) larger than the Infinity
+    Cache? Then the K rows a mix shares with the previous one come from HBM again, and the fused
+    round (``RingPopulationShard(fused="auto")``), which reads every row once, engages. Below that
+    size consecutive per-device mixes re-read their shared rows from the cache."""
+    return (K + 1) * P * itemsize > INFINITY_CACHE_BYTES
+
+
+def split_runs(devices: List[int], whole) -> List[Tuple[List[int], bool]]:
+    """``devices`` in the given order, cut into [(run, fusable)]: a fusable run is a maximal
+    stretch of consecutive ascending local devices (i, i + 1, ...) for each of which ``whole(i)``
+    holds (its whole window lies in the shard's own stack); every other device is a run of its own
+    with fusable False. Pure host logic."""
+    runs: List[Tuple[List[int], bool]] = []
+    for i in devices:
+        ok = bool(whole(i))
+        if ok and runs and runs[-1][1] and runs[-1][0][-1] + 1 == i:
+            runs[-1][0].append(i)
+        else:
+            runs.append(([i], ok))
+    return runs
+
 
 def partition_shape(partition: str, world: int, devices: int, dev_groups: Optional[int] = None
                     ) -> Tuple[int, int]:
@@ -170,10 +195,19 @@ class RingPopulationShard:
 
     def __init__(self, plan: RingShardPlan, P: int, device, transport=None, engine=None,
                  dtype=torch.float32, window_batch: int = 0, route=None, rank: Optional[int] = None,
-                 stacks: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, carve: bool = False):
+                 stacks: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, carve: bool = False,
+                 fused="auto"):
         """``window_batch`` = B > 0 mixes B consecutive devices per ``cfa_mix_window_f32`` pass,
         loading each row of their shared window once (identical results); 0 = one streaming
         mix per device.
+
+        ``fused`` (with ``window_batch`` 0): a run of two or more consecutive devices whose whole
+        windows lie in the ``models`` stack (the whole ring at world 1, the interior otherwise) is
+        mixed by ONE ``cfa_mix_ring_slide_f32`` call that reads every row once (identical results).
+        ``"auto"`` (default) does so only when a window's (K + 1) rows exceed the Infinity Cache
+        (``window_exceeds_cache``), ``True`` at every size, ``False`` never. Boundary devices, runs
+        of one device (a scattered ``mix_order``), engines without ``ring_slide``, other dtypes and
+        rows that are not 16-byte aligned keep one mix per device.
 
         ``route`` (a ``halo.RoutePlan`` over the global ranks, e.g. from ``make_ring_shard``)
         replaces the single grouped exchange: the halo travels in stages over direct and relayed
@@ -189,9 +223,18 @@ class RingPopulationShard:
         the halo is allocated on its own, as it is without ``carve``."""
         if window_batch and not (1 <= window_batch <= 8 and plan.hl <= 4 and plan.hr <= 4):
             raise ValueError("window_batch must be 1..8 with at most 4 neighbours per side")
+        if fused not in ("auto", True, False):
+            raise ValueError('fused must be "auto", True or False')
         self.window_batch = int(window_batch)
+        self.fused = fused
         self.plan, self.P = plan, int(P)
         self.device = torch.device(device)
+        # the fused round's per-device coefficients, [L] fp32 on the device, built once. A round may
+        # run on any stream, so the fill is finished here, on the host, before the shard is used
+        self._slide_alphas = None
+        if self.device.type == "cuda" and fused is not False and not window_batch:
+            self._slide_alphas = torch.full((plan.L,), 1.0 / (plan.K + 1), dtype=torch.float32, device=self.device)
+            torch.cuda.current_stream(self.device).synchronize()
         if stacks is not None:
             for t in stacks:
                 same_dev = t.device.type == self.device.type and (self.device.index is None
@@ -333,6 +376,34 @@ class RingPopulationShard:
         rows = [self.bucket((g0 + o) % p.D) for o in range(-p.hl, len(devs) + p.hr)]
         self.engine.mix_window([self.mixed[i] for i in devs], rows, [self.alphas] * len(devs), p.hl, p.hr, stream)
 
+    def fuses(self) -> bool:
+        """Does a run of consecutive whole-window devices take the one-call sliding round here?"""
+        p = self.plan
+        if self.window_batch or self.fused is False or not callable(getattr(self.engine, "ring_slide", None)):
+            return False
+        m, o = self.models, self.mixed
+        if m.dtype != torch.float32 or not m.is_cuda or self.P % 4 or p.hl > 4 or p.hr > 4 or p.K >= p.L:
+            return False
+        for t in (m, o):
+            if t.data_ptr() % 16 or (t.shape[1] > 1 and t.stride(1) != 1) or (p.L > 1 and t.stride(0) % 4):
+                return False
+        return self.fused is True or window_exceeds_cache(self.P, p.K, m.element_size())
+
+    def mix_runs(self, devices: List[int]) -> List[Tuple[List[int], bool]]:
+        """``devices`` as [(run, fused)]: runs of two or more consecutive devices with their whole
+        windows in the ``models`` stack are fused, every other device is a run of its own."""
+        return [(run, ok and len(run) >= 2)
+                for run, ok in split_runs(devices, lambda i: not self.plan.needs_halo(i))]
+
+    def mix_run(self, run: List[int], stream=None) -> None:
+        """One cfa_mix_ring_slide_f32 call over consecutive local devices ``run``."""
+        p = self.plan
+        if self._slide_alphas is None:  # ``fused`` switched on after construction: as in __init__
+            self._slide_alphas = torch.full((p.L,), 1.0 / (p.K + 1), dtype=torch.float32, device=self.device)
+            torch.cuda.current_stream(self.device).synchronize()
+        self.engine.ring_slide(self.mixed, self.models, self._slide_alphas[:len(run)], run[0], len(run),
+                               p.hl, p.hr, stream)
+
     def _mix_set(self, devices: List[int], stream, timer=None, between=None) -> None:
         """Mix ``devices`` on ``stream``; ``between()`` (optional) after each launch (the host
         lane's non-blocking pump, so an H2D whose chunk has arrived is enqueued at once)."""
@@ -346,12 +417,19 @@ class RingPopulationShard:
                 if between:
                     between()
             return
-        for i in devices:
+        if self.fuses():
+            runs = self.mix_runs(devices)
+        else:
+            runs = [([i], False) for i in devices]
+        for run, fused in runs:
             if timer:
-                timer(i, True)
-            self.mix_device(i, stream)
+                timer(run[0], True)
+            if fused:
+                self.mix_run(run, stream)
+            else:
+                self.mix_device(run[0], stream)
             if timer:
-                timer(i, False)
+                timer(run[-1], False)
             if between:
                 between()
 
@@ -505,7 +583,7 @@ def make_ring_shard(rank: int, world: int, devices: int, hl: int, hr: int, P: in
                     window_batch: int = 0, dtype=torch.float32, placement_candidates: int = 0,
                     placement_release: bool = False, link_rates=None, message_us: float = 0.0,
                     lane_token: Optional[str] = None, lane_agree=None, lane_chunk_elems: Optional[int] = None,
-                    lane_numa_nodes=None):
+                    lane_numa_nodes=None, fused="auto"):
     """The shard of global rank ``rank`` for a fixed population of ``devices`` ring devices
     (strong scaling: the population does not grow with ``world``).
 
@@ -523,7 +601,8 @@ def make_ring_shard(rank: int, world: int, devices: int, hl: int, hr: int, P: in
     is offered to the route too; if the chosen route uses it the shard's lane is opened here
     (collective: every rank passes the same ``lane_token`` and ``lane_agree``, the control plane's
     all-ranks AND; ``lane_numa_nodes[r]``: the NUMA node of rank r's GPU, where the segments rank
-    r receives are placed)."""
+    r receives are placed). ``fused``: as for ``RingPopulationShard`` (the one-call sliding round for
+    runs of consecutive devices, by default where a window exceeds the Infinity Cache)."""
     from .halo import choose_route, ring_transfers
     gd, gp = partition_shape(partition, world, devices, dev_groups)
     d, p = divmod(rank, gp)
@@ -549,7 +628,7 @@ def make_ring_shard(rank: int, world: int, devices: int, hl: int, hr: int, P: in
                                                      dtype=dtype, release=placement_release)
         stacks = (models, mixed)
     shard = RingPopulationShard(plan, Pr, device, transport, engine, dtype, window_batch, route=route, rank=rank,
-                                stacks=stacks, carve=stacks is not None)
+                                stacks=stacks, carve=stacks is not None, fused=fused)
     if route is not None and route.lane:
         shard.open_lane(lane_token, lane_agree, chunk_elems=chunk, numa_nodes=lane_numa_nodes)
     info = {"partition": partition, "device_groups": gd, "param_slices": gp,

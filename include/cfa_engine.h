@@ -476,6 +476,22 @@ CFA_API int cfa_mix_window_f32(float* const* out, const float* const* rows, cons
 CFA_API int cfa_mix_ring_round_f32(float* out, const float* in, size_t pitch, const float* alphas, int D,
                                    int hl, int hr, size_t P, void* stream);
 
+/* (e/f4) A run of consecutive ring devices of a STACKED population with every row read once and
+ * every output written once: devices first .. first+count-1 of a stack of `rows` rows (row r of the
+ * input at in + r * in_pitch, of the output at out + r * out_pitch, P floats each). Device d mixes
+ * its row with rows (d-hl .. d-1, d+1 .. d+hr) mod rows in that order, coefficient
+ * alphas[d - first] (DEVICE array of count floats) at each step, and writes row d mod rows of out;
+ * the run may pass the last row only when count == rows (the whole ring). Each workgroup slides a
+ * register window of hl+hr+1 rows down a segment of the run, so a call moves
+ * (2 * count + segments * (hl+hr)) * P * 4 bytes against count * (hl+hr+2) * P * 4 for per-device
+ * mixes, with identical results. Launch shape (environment, read at each launch, results
+ * identical): CFA_SLIDE_SEGMENTS, CFA_SLIDE_WG_PER_CU, CFA_SLIDE_PF (rows prefetched, 1..4),
+ * CFA_SLIDE_SC1 (write-through stores). CFA_E_UNSUPPORTED unless rows are 16-byte aligned (bases,
+ * pitches and P multiples of 4 floats); out must not overlap in. */
+CFA_API int cfa_mix_ring_slide_f32(float* out, size_t out_pitch, const float* in, size_t in_pitch,
+                                   const float* alphas, int rows, int first, int count, int hl, int hr,
+                                   size_t P, void* stream);
+
 /* (f3) CFA-GE neighbour-gradient evaluation: the gradient of a device's own cost at each of M
  * neighbour models, for the two TF1 graphs of cfa_ge_2stage.py (:391-433 graph, :512-528 one
  * Session per neighbour; cfa_ge_4stage.py the same), one workgroup per model, fp32 like the
