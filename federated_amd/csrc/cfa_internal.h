@@ -168,6 +168,21 @@ static unsigned grid_for_own(long long tiles, int own_blocks_per_cu) {
   return grid_for(tiles, t);
 }
 
+// grid.x of a launch whose gy rows of workgroups (grid.y) share the device: about wg_per_cu
+// workgroups per CU over all rows, at most one per tile, at least one.
+static unsigned shared_grid_x(long long tiles, int wg_per_cu, long long gy) {
+  long long gx = ((long long)device_cus() * wg_per_cu + gy - 1) / gy;
+  if (gx > tiles) gx = tiles;
+  if (gx < 1) gx = 1;
+  return (unsigned)gx;
+}
+
+// An environment override as atoi reads it (0 for text that is no number); `unset` without one.
+static int env_int(const char* name, int unset) {
+  const char* s = getenv(name);
+  return s ? atoi(s) : unset;
+}
+
 // Kernel-argument pack: pointers + coefficients land in SGPRs.
 struct Fanin {
   const float* src[CFA_MAX_FANIN + 1];  // [0] = local (w0), [1..N] = neighbours
@@ -232,16 +247,22 @@ __device__ __forceinline__ void st4(float* p, long long i, f4 v) {
   else *q = v;
 }
 
+// One step of the sequential rule on a float4 or a float: three separately rounded fp32
+// operations (-ffp-contract=off), as fp32 numpy evaluates w + eps * (x - w). Every sequential
+// fold of the library steps through here; every bit-for-bit claim rests on it.
+template <typename T>
+__device__ __forceinline__ T seq_step(T acc, T x, float a) {
+  T t = x - acc;   // numpy: (x - w)
+  t = a * t;       //        eps * (...)
+  return acc + t;  //        w + (...)
+}
+
 template <int N, int RULE>
 __device__ __forceinline__ f4 fold(const f4 (&v)[N + 1], const Fanin& f) {
   if constexpr (RULE == CFA_RULE_SEQUENTIAL) {
     f4 w = v[0];
 #pragma unroll
-    for (int j = 1; j <= N; ++j) {
-      f4 t = v[j] - w;  // numpy: (x - w)
-      t = f.c[j] * t;   //        eps * (...)
-      w = w + t;        //        w + (...)
-    }
+    for (int j = 1; j <= N; ++j) w = seq_step(w, v[j], f.c[j]);
     return w;
   } else if constexpr (RULE == CFA_RULE_SEQUENTIAL_DIV) {
     f4 w = v[0];
@@ -358,10 +379,29 @@ constexpr long long kMaxChunkVec = 1LL << 27;
 constexpr int kStoreSc1 = 16;
 constexpr int kStoreNt = 2;
 
+// The host side of that split: fn(done, m) for each chunk of m <= kMaxChunkVec float4 at `done`.
+template <typename F>
+inline void for_each_chunk(long long nvec, F&& fn) {
+  for (long long done = 0; done < nvec; done += kMaxChunkVec)
+    fn(done, (nvec - done) < kMaxChunkVec ? (nvec - done) : kMaxChunkVec);
+}
+
+// The streaming buffer store: the output resource of a chunk of `bytes` bytes (16 per float4, at
+// most 2 GiB), and the store of 16-byte vector idx of it (a 32-bit byte offset) with a
+// compile-time policy (kStoreSc1 / kStoreNt).
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t out_rsrc(void* base, unsigned bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(base, 0, bytes, 0x00020000);
+}
+template <int POLICY, typename V>
+__device__ __forceinline__ void st16_buf(__amdgpu_buffer_rsrc_t r, long long idx, V v) {
+  static_assert(sizeof(V) == 16, "16-byte vectors only");
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, v), r, (int)(idx * 16), 0, POLICY);
+}
+
 // Streaming store of one 16-byte vector with the sc1 write-through policy, as the headline mix
-// stores its output (kStoreSc1): through a buffer resource when every byte offset of the output
-// fits the 31 bits the kernels pass, else a nontemporal global store. The choice is uniform per
-// launch (one scalar branch).
+// stores its output (kStoreSc1), for outputs the host does not chunk: through the buffer store
+// when every byte offset of the output fits the 31 bits the kernels pass, else a nontemporal
+// global store. The choice is uniform per launch (one scalar branch).
 struct Sc1Out {
   __amdgpu_buffer_rsrc_t r;
   void* base;
@@ -371,14 +411,13 @@ __device__ __forceinline__ Sc1Out sc1_out(void* base, long long bytes) {
   Sc1Out o;
   o.base = base;
   o.buf = bytes <= 0x7FFFFFF0LL;
-  o.r = __builtin_amdgcn_make_buffer_rsrc(base, 0, o.buf ? (unsigned)bytes : 0u, 0x00020000);
+  o.r = out_rsrc(base, o.buf ? (unsigned)bytes : 0u);
   return o;
 }
 template <typename V>
 __device__ __forceinline__ void st16_sc1(const Sc1Out& o, long long idx, V v) {  // idx: 16-byte units
-  static_assert(sizeof(V) == 16, "16-byte vectors only");
   if (o.buf)
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, v), o.r, (int)(idx * 16), 0, kStoreSc1);
+    st16_buf<kStoreSc1>(o.r, idx, v);
   else
     __builtin_nontemporal_store(v, reinterpret_cast<V*>(o.base) + idx);
 }

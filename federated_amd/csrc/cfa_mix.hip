@@ -139,8 +139,7 @@ __global__ __launch_bounds__(kBlock) void mix_vec_kernel(float* out, Fanin f, lo
   constexpr long long kTile = (long long)kBlock * U;
   const long long full = nvec / kTile;
   // (unused and removed by the compiler when POL == 0)
-  const __amdgpu_buffer_rsrc_t w =
-      __builtin_amdgcn_make_buffer_rsrc((void*)out, 0, (unsigned)(nvec * 16), 0x00020000);
+  const __amdgpu_buffer_rsrc_t w = out_rsrc(out, (unsigned)(nvec * 16));
   for (long long t = blockIdx.x; t < full; t += gridDim.x) {
     const long long base = t * kTile + threadIdx.x;
     f4 v[U][N + 1];
@@ -152,9 +151,7 @@ __global__ __launch_bounds__(kBlock) void mix_vec_kernel(float* out, Fanin f, lo
     for (int u = 0; u < U; ++u) {
       const f4 y = fold<N, RULE>(v[u], f);
       if constexpr (POL != 0)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, y), w,
-                                               (int)((base + (long long)u * kBlock) * 16), 0,
-                                               POL == 2 ? kStoreNt : kStoreSc1);
+        st16_buf<POL == 2 ? kStoreNt : kStoreSc1>(w, base + (long long)u * kBlock, y);
       else
         st4<false>(out, base + (long long)u * kBlock, y);
     }
@@ -227,12 +224,15 @@ __global__ __launch_bounds__(kBlock) void mix_scalar_kernel(float* out, ScalarFa
        i += (long long)gridDim.x * kBlock) {
     const float w0 = f.src[0][i];
     float w;
-    if (rule == CFA_RULE_SEQUENTIAL || rule == CFA_RULE_SEQUENTIAL_DIV) {
+    if (rule == CFA_RULE_SEQUENTIAL) {
+      w = w0;
+      for (int j = 1; j <= f.n; ++j) w = seq_step(w, f.src[j][i], f.c[j]);
+    } else if (rule == CFA_RULE_SEQUENTIAL_DIV) {
       w = w0;
       for (int j = 1; j <= f.n; ++j) {
         float t = f.src[j][i] - w;
         t = f.c[j] * t;
-        if (rule == CFA_RULE_SEQUENTIAL_DIV) t = t / f.d[j];
+        t = t / f.d[j];  // between the multiply and the add: not seq_step
         w = w + t;
       }
     } else {
@@ -320,13 +320,11 @@ static void launch_vec_chunk(int n, hipStream_t st, float* out, const Fanin& f, 
 template <int RULE>
 static void launch_vec(int n, hipStream_t st, float* out, const Fanin& f, long long nvec,
                        const cfa_launch_t& t) {
-  // chunks of at most kMaxChunkVec float4 (32-bit buffer offsets of the streaming store)
-  for (long long done = 0; done < nvec; done += kMaxChunkVec) {
-    const long long m = (nvec - done) < kMaxChunkVec ? (nvec - done) : kMaxChunkVec;
+  for_each_chunk(nvec, [&](long long done, long long m) {
     Fanin g = f;
     for (int k = 0; k <= n; ++k) g.src[k] = f.src[k] + done * 4;
     launch_vec_chunk<RULE>(n, st, out + done * 4, g, m, t);
-  }
+  });
 }
 
 template <int RULE>

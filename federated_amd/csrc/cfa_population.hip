@@ -2,14 +2,15 @@
 // (cfa_mix_population_f32) and the sliding-window passes (cfa_mix_window_f32) that load each
 // row of a ring window once for up to 8 consecutive devices, and the sliding ring round
 // (cfa_mix_ring_slide_f32) that reads every row of a run of ring devices once.
+#include <type_traits>
+
 #include "cfa_internal.h"
 
 // Resident workgroups per CU across a whole population launch (all devices together). 8 by
 // default; CFA_POP_WG_PER_CU overrides it per call (read at each launch, so one process can
 // compare values: tools/probe/pop_shape.py).
 static int pop_wg_per_cu() {
-  const char* s = getenv("CFA_POP_WG_PER_CU");
-  const int v = s ? atoi(s) : 0;
+  const int v = env_int("CFA_POP_WG_PER_CU", 8);
   return v > 0 ? v : 8;
 }
 
@@ -56,9 +57,7 @@ __global__ __launch_bounds__(kBlock) void population_kernel(float* const* out_pt
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         if constexpr (RULE == CFA_RULE_SEQUENTIAL) {
-          f4 tt = x[u] - w[u];
-          tt = c * tt;
-          w[u] = w[u] + tt;
+          w[u] = seq_step(w[u], x[u], c);
         } else {
           w[u].x = fmaf(c, x[u].x, w[u].x);
           w[u].y = fmaf(c, x[u].y, w[u].y);
@@ -81,9 +80,7 @@ __global__ __launch_bounds__(kBlock) void population_kernel(float* const* out_pt
       const float x = src_ptrs[csr_idx[e]][i];
       const float c = csr_coef[e];
       if constexpr (RULE == CFA_RULE_SEQUENTIAL) {
-        float tt = x - w;
-        tt = c * tt;
-        w = w + tt;
+        w = seq_step(w, x, c);
       } else {
         w = fmaf(c, x, w);
       }
@@ -178,21 +175,16 @@ struct WindowArgs {
   int nb;
 };
 
-template <int HL, int HR>
-__device__ __forceinline__ f4 window_fold(const f4* r, int b, const WindowArgs& w) {
-  f4 acc = r[b + HL];
+// The fold of one ring device over its window's HL + HR + 1 rows, row(j) = the j-th row of the
+// window (the local row is row(HL)): the local row, then the rows below in ascending order, then
+// the rows above, as the reference window's order.
+template <int HL, int HR, typename Row>
+__device__ __forceinline__ f4 ring_fold(Row row, float a) {
+  f4 acc = row(HL);
 #pragma unroll
-  for (int j = 0; j < HL; ++j) {
-    f4 t = r[b + j] - acc;
-    t = w.a[b] * t;
-    acc = acc + t;
-  }
+  for (int j = 0; j < HL; ++j) acc = seq_step(acc, row(j), a);
 #pragma unroll
-  for (int j = 0; j < HR; ++j) {
-    f4 t = r[b + HL + 1 + j] - acc;
-    t = w.a[b] * t;
-    acc = acc + t;
-  }
+  for (int j = 0; j < HR; ++j) acc = seq_step(acc, row(HL + 1 + j), a);
   return acc;
 }
 
@@ -216,15 +208,14 @@ __device__ __forceinline__ void window_body(const WindowArgs& w, long long nvec)
     for (int b = 0; b < kWinMaxDev; ++b)
       if (b < w.nb) {
         // (unused and removed by the compiler when !SC1) write-through streaming store
-        const __amdgpu_buffer_rsrc_t o =
-            __builtin_amdgcn_make_buffer_rsrc((void*)w.out[b], 0, (unsigned)(nvec * 16), 0x00020000);
+        const __amdgpu_buffer_rsrc_t o = out_rsrc(w.out[b], (unsigned)(nvec * 16));
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           const long long i = base + (long long)u * kBlock;
           if (i < nvec) {
-            const f4 y = window_fold<HL, HR>(r[u], b, w);
+            const f4 y = ring_fold<HL, HR>([&](int j) { return r[u][b + j]; }, w.a[b]);
             if constexpr (SC1)
-              __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, y), o, (int)(i * 16), 0, kStoreSc1);
+              st16_buf<kStoreSc1>(o, i, y);
             else
               st4<true>(w.out[b], i, y);
           }
@@ -278,8 +269,8 @@ __global__ __launch_bounds__(kBlock) void ring_round_kernel(RingArgs ra, long lo
 // device m of the segment folds stream rows m .. m+W-1 (its local row is m+HL) while the loads of
 // rows m+W .. m+W-1+PF are in flight. The device loop is unrolled W + PF times, so stream row q
 // always sits in slot q mod (W + PF) and every register index is static. A segment re-reads HL+HR
-// halo rows: a call reads count + segments * (HL+HR) rows. The fold is window_fold's: local row,
-// rows below in ascending order, rows above, t = x - acc; t = a*t; acc = acc + t.
+// halo rows: a call reads count + segments * (HL+HR) rows. The fold is the window pass's
+// (ring_fold), on the slots the window's rows sit in.
 // ------------------------------------------------------------------------------------------
 struct SlideArgs {
   const float* in;
@@ -330,27 +321,11 @@ __global__ __launch_bounds__(kBlock) void ring_slide_kernel(SlideArgs sa, long l
             rp += sa.in_pitch;
             if (rp == in_end) rp = in;
           }
-          const float a = sa.alphas[n0 + m];
-          f4 acc = r[(u + HL) % RS];
-#pragma unroll
-          for (int j = 0; j < HL; ++j) {
-            f4 x = r[(u + j) % RS] - acc;
-            x = a * x;
-            acc = acc + x;
-          }
-#pragma unroll
-          for (int j = 0; j < HR; ++j) {
-            f4 x = r[(u + HL + 1 + j) % RS] - acc;
-            x = a * x;
-            acc = acc + x;
-          }
-          if constexpr (SC1) {
-            const __amdgpu_buffer_rsrc_t o =
-                __builtin_amdgcn_make_buffer_rsrc((void*)op, 0, (unsigned)(nvec * 16), 0x00020000);
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, acc), o, (int)voff, 0, kStoreSc1);
-          } else {
+          const f4 acc = ring_fold<HL, HR>([&](int j) { return r[(u + j) % RS]; }, sa.alphas[n0 + m]);
+          if constexpr (SC1)
+            st16_buf<kStoreSc1>(out_rsrc(op, (unsigned)(nvec * 16)), i, acc);
+          else
             __builtin_nontemporal_store(acc, reinterpret_cast<f4*>(reinterpret_cast<char*>(op) + voff));
-          }
           op += sa.out_pitch;
           if (op == out_end) op = out;
         }
@@ -366,16 +341,8 @@ __global__ __launch_bounds__(kBlock) void window_scalar_kernel(WindowArgs w, int
        i += (long long)gridDim.x * kBlock) {
     for (int b = 0; b < w.nb; ++b) {
       float acc = w.rows[b + hl][i];
-      for (int j = 0; j < hl; ++j) {
-        float t = w.rows[b + j][i] - acc;
-        t = w.a[b] * t;
-        acc = acc + t;
-      }
-      for (int j = 0; j < hr; ++j) {
-        float t = w.rows[b + hl + 1 + j][i] - acc;
-        t = w.a[b] * t;
-        acc = acc + t;
-      }
+      for (int j = 0; j < hl; ++j) acc = seq_step(acc, w.rows[b + j][i], w.a[b]);
+      for (int j = 0; j < hr; ++j) acc = seq_step(acc, w.rows[b + hl + 1 + j][i], w.a[b]);
       w.out[b][i] = acc;
     }
   }
@@ -389,74 +356,63 @@ struct WindowTune {
 };
 static WindowTune window_tune() {  // env overrides for tools/tune_window.py; results identical
   WindowTune t{1, 0, 6};  // tools/tune_window.py, profiles/r01_tune_window.jsonl
-  if (const char* e = getenv("CFA_WINDOW_VEC")) t.vec = atoi(e) == 1 ? 1 : 2;
-  if (const char* e = getenv("CFA_WINDOW_SC1")) t.sc1 = atoi(e) ? 1 : 0;
-  if (const char* e = getenv("CFA_WINDOW_BLOCKS_PER_CU")) t.blocks_per_cu = atoi(e) > 0 ? atoi(e) : 2;
+  t.vec = env_int("CFA_WINDOW_VEC", t.vec) == 1 ? 1 : 2;
+  t.sc1 = env_int("CFA_WINDOW_SC1", t.sc1) ? 1 : 0;
+  t.blocks_per_cu = env_int("CFA_WINDOW_BLOCKS_PER_CU", t.blocks_per_cu);
+  if (t.blocks_per_cu <= 0) t.blocks_per_cu = 2;  // kept as it is: not the default 6
   return t;
+}
+static long long window_tiles(long long m, const WindowTune& t) {
+  return (m + (long long)kBlock * t.vec - 1) / ((long long)kBlock * t.vec);
+}
+// The run-time (vec, sc1) of a window launch as the kernels' <U, SC1>: fn(U, SC1) gets them as
+// std::integral_constant values.
+template <typename F>
+void for_vec_sc1(const WindowTune& t, F&& fn) {
+  using One = std::integral_constant<int, 1>;
+  using Two = std::integral_constant<int, 2>;
+  if (t.vec == 1) {
+    if (t.sc1) fn(One{}, std::true_type{});
+    else fn(One{}, std::false_type{});
+  } else {
+    if (t.sc1) fn(Two{}, std::true_type{});
+    else fn(Two{}, std::false_type{});
+  }
 }
 template <int HL, int HR>
 void launch_window(const WindowArgs& w, long long nvec, hipStream_t st) {
   const WindowTune t = window_tune();
   const cfa_launch_t lc{t.blocks_per_cu, t.vec, 1};
-  // chunks of at most kMaxChunkVec float4: 32-bit buffer offsets of the streaming store
-  for (long long done = 0; done < nvec; done += kMaxChunkVec) {
-    const long long m = (nvec - done) < kMaxChunkVec ? (nvec - done) : kMaxChunkVec;
+  for_each_chunk(nvec, [&](long long done, long long m) {
     WindowArgs c = w;
     for (int k = 0; k < w.nb + HL + HR; ++k) c.rows[k] = w.rows[k] + done * 4;
     for (int b = 0; b < w.nb; ++b) c.out[b] = w.out[b] + done * 4;
-    const long long tiles = (m + (long long)kBlock * t.vec - 1) / ((long long)kBlock * t.vec);
-    const unsigned grid = grid_for(tiles, lc);
-    if (t.vec == 1) {
-      if (t.sc1) window_vec_kernel<HL, HR, 1, true><<<grid, kBlock, 0, st>>>(c, m);
-      else window_vec_kernel<HL, HR, 1, false><<<grid, kBlock, 0, st>>>(c, m);
-    } else {
-      if (t.sc1) window_vec_kernel<HL, HR, 2, true><<<grid, kBlock, 0, st>>>(c, m);
-      else window_vec_kernel<HL, HR, 2, false><<<grid, kBlock, 0, st>>>(c, m);
-    }
-  }
+    const unsigned grid = grid_for(window_tiles(m, t), lc);
+    for_vec_sc1(t, [&](auto u, auto sc1) {
+      window_vec_kernel<HL, HR, decltype(u)::value, decltype(sc1)::value><<<grid, kBlock, 0, st>>>(c, m);
+    });
+  });
 }
 template <int HL, int HR>
 void launch_ring_round(const RingArgs& ra, long long nvec, hipStream_t st) {
   const WindowTune t = window_tune();
   const cfa_launch_t lc{t.blocks_per_cu, t.vec, 1};
   const unsigned passes = (unsigned)((ra.D + kWinMaxDev - 1) / kWinMaxDev);
-  for (long long done = 0; done < nvec; done += kMaxChunkVec) {
-    const long long m = (nvec - done) < kMaxChunkVec ? (nvec - done) : kMaxChunkVec;
+  for_each_chunk(nvec, [&](long long done, long long m) {
     RingArgs c = ra;
     c.off = ra.off + done * 4;
-    const long long tiles = (m + (long long)kBlock * t.vec - 1) / ((long long)kBlock * t.vec);
-    // the launch's blocks over all passes: about blocks_per_cu per CU in all
+    const long long tiles = window_tiles(m, t);
+    // the launch's blocks over all passes: about blocks_per_cu per CU in all. Not shared_grid_x:
+    // the tiles are capped before the division by the passes (10 tiles over 16 passes give 1, not 10)
     long long gx = (grid_for(tiles, lc) + passes - 1) / passes;
     if (gx < 1) gx = 1;
     if (gx > tiles) gx = tiles;
     const dim3 grid((unsigned)gx, passes);
-    if (t.vec == 1) {
-      if (t.sc1) ring_round_kernel<HL, HR, 1, true><<<grid, kBlock, 0, st>>>(c, m);
-      else ring_round_kernel<HL, HR, 1, false><<<grid, kBlock, 0, st>>>(c, m);
-    } else {
-      if (t.sc1) ring_round_kernel<HL, HR, 2, true><<<grid, kBlock, 0, st>>>(c, m);
-      else ring_round_kernel<HL, HR, 2, false><<<grid, kBlock, 0, st>>>(c, m);
-    }
-  }
+    for_vec_sc1(t, [&](auto u, auto sc1) {
+      ring_round_kernel<HL, HR, decltype(u)::value, decltype(sc1)::value><<<grid, kBlock, 0, st>>>(c, m);
+    });
+  });
 }
-using RingLaunch = void (*)(const RingArgs&, long long, hipStream_t);
-#define CFA_R(L, R) &launch_ring_round<L, R>
-const RingLaunch kRingLaunch[5][5] = {
-    {CFA_R(0, 0), CFA_R(0, 1), CFA_R(0, 2), CFA_R(0, 3), CFA_R(0, 4)},
-    {CFA_R(1, 0), CFA_R(1, 1), CFA_R(1, 2), CFA_R(1, 3), CFA_R(1, 4)},
-    {CFA_R(2, 0), CFA_R(2, 1), CFA_R(2, 2), CFA_R(2, 3), CFA_R(2, 4)},
-    {CFA_R(3, 0), CFA_R(3, 1), CFA_R(3, 2), CFA_R(3, 3), CFA_R(3, 4)},
-    {CFA_R(4, 0), CFA_R(4, 1), CFA_R(4, 2), CFA_R(4, 3), CFA_R(4, 4)}};
-#undef CFA_R
-using WindowLaunch = void (*)(const WindowArgs&, long long, hipStream_t);
-#define CFA_W(L, R) &launch_window<L, R>
-const WindowLaunch kWindowLaunch[5][5] = {
-    {CFA_W(0, 0), CFA_W(0, 1), CFA_W(0, 2), CFA_W(0, 3), CFA_W(0, 4)},
-    {CFA_W(1, 0), CFA_W(1, 1), CFA_W(1, 2), CFA_W(1, 3), CFA_W(1, 4)},
-    {CFA_W(2, 0), CFA_W(2, 1), CFA_W(2, 2), CFA_W(2, 3), CFA_W(2, 4)},
-    {CFA_W(3, 0), CFA_W(3, 1), CFA_W(3, 2), CFA_W(3, 3), CFA_W(3, 4)},
-    {CFA_W(4, 0), CFA_W(4, 1), CFA_W(4, 2), CFA_W(4, 3), CFA_W(4, 4)}};
-#undef CFA_W
 
 // Launch shape of the sliding ring round. The environment overrides are read at each launch, so
 // one process can compare shapes on the same buffers (tools/probe/ring_slide.py); results are
@@ -465,11 +421,12 @@ struct SlideTune {
   int segments, wg_per_cu, pf, sc1;
 };
 static SlideTune slide_tune() {
-  SlideTune t{1, 4, 2, 0};  // tools/probe/ring_slide.py sweep, profiles/r07_ring_slide_sweep.jsonl
-  if (const char* e = getenv("CFA_SLIDE_SEGMENTS")) t.segments = atoi(e) > 0 ? atoi(e) : t.segments;
-  if (const char* e = getenv("CFA_SLIDE_WG_PER_CU")) t.wg_per_cu = atoi(e) > 0 ? atoi(e) : t.wg_per_cu;
-  if (const char* e = getenv("CFA_SLIDE_PF")) t.pf = atoi(e) >= 1 && atoi(e) <= 4 ? atoi(e) : t.pf;
-  if (const char* e = getenv("CFA_SLIDE_SC1")) t.sc1 = atoi(e) ? 1 : 0;
+  const SlideTune d{1, 4, 2, 0};  // tools/probe/ring_slide.py sweep, profiles/r07_ring_slide_sweep.jsonl
+  SlideTune t{env_int("CFA_SLIDE_SEGMENTS", d.segments), env_int("CFA_SLIDE_WG_PER_CU", d.wg_per_cu),
+              env_int("CFA_SLIDE_PF", d.pf), env_int("CFA_SLIDE_SC1", d.sc1) ? 1 : 0};
+  if (t.segments <= 0) t.segments = d.segments;
+  if (t.wg_per_cu <= 0) t.wg_per_cu = d.wg_per_cu;
+  if (t.pf < 1 || t.pf > 4) t.pf = d.pf;
   return t;
 }
 template <int HL, int HR, int PF>
@@ -485,32 +442,28 @@ void launch_ring_slide(const SlideArgs& sa, long long nvec, hipStream_t st) {
   SlideArgs c = sa;
   c.seg = (sa.count + segments - 1) / segments;
   const unsigned gy = (unsigned)((sa.count + c.seg - 1) / c.seg);  // no empty segment
-  for (long long done = 0; done < nvec; done += kMaxChunkVec) {
-    const long long m = (nvec - done) < kMaxChunkVec ? (nvec - done) : kMaxChunkVec;
+  for_each_chunk(nvec, [&](long long done, long long m) {
     c.off = done * 4;
-    const long long tiles = (m + kBlock - 1) / kBlock;
     // the launch's workgroups over all segments: about wg_per_cu per CU in all
-    long long gx = ((long long)device_cus() * t.wg_per_cu + gy - 1) / gy;
-    if (gx > tiles) gx = tiles;
-    if (gx < 1) gx = 1;
-    const dim3 grid((unsigned)gx, gy);
+    const dim3 grid(shared_grid_x((m + kBlock - 1) / kBlock, t.wg_per_cu, gy), gy);
     switch (t.pf) {
       case 1: launch_slide_pf<HL, HR, 1>(c, m, grid, t.sc1, st); break;
       case 3: launch_slide_pf<HL, HR, 3>(c, m, grid, t.sc1, st); break;
       case 4: launch_slide_pf<HL, HR, 4>(c, m, grid, t.sc1, st); break;
       default: launch_slide_pf<HL, HR, 2>(c, m, grid, t.sc1, st); break;
     }
-  }
+  });
 }
-using SlideLaunch = void (*)(const SlideArgs&, long long, hipStream_t);
-#define CFA_S(L, R) &launch_ring_slide<L, R>
-const SlideLaunch kSlideLaunch[5][5] = {
-    {CFA_S(0, 0), CFA_S(0, 1), CFA_S(0, 2), CFA_S(0, 3), CFA_S(0, 4)},
-    {CFA_S(1, 0), CFA_S(1, 1), CFA_S(1, 2), CFA_S(1, 3), CFA_S(1, 4)},
-    {CFA_S(2, 0), CFA_S(2, 1), CFA_S(2, 2), CFA_S(2, 3), CFA_S(2, 4)},
-    {CFA_S(3, 0), CFA_S(3, 1), CFA_S(3, 2), CFA_S(3, 3), CFA_S(3, 4)},
-    {CFA_S(4, 0), CFA_S(4, 1), CFA_S(4, 2), CFA_S(4, 3), CFA_S(4, 4)}};
-#undef CFA_S
+
+// The launchers by (hl, hr), each 0..4: the one definition of the 5x5 table.
+#define CFA_HLHR_ROW(F, L) {&F<L, 0>, &F<L, 1>, &F<L, 2>, &F<L, 3>, &F<L, 4>}
+#define CFA_HLHR_TABLE(F) \
+  {CFA_HLHR_ROW(F, 0), CFA_HLHR_ROW(F, 1), CFA_HLHR_ROW(F, 2), CFA_HLHR_ROW(F, 3), CFA_HLHR_ROW(F, 4)}
+void (*const kWindowLaunch[5][5])(const WindowArgs&, long long, hipStream_t) = CFA_HLHR_TABLE(launch_window);
+void (*const kRingLaunch[5][5])(const RingArgs&, long long, hipStream_t) = CFA_HLHR_TABLE(launch_ring_round);
+void (*const kSlideLaunch[5][5])(const SlideArgs&, long long, hipStream_t) = CFA_HLHR_TABLE(launch_ring_slide);
+#undef CFA_HLHR_TABLE
+#undef CFA_HLHR_ROW
 }  // namespace
 
 extern "C" int cfa_mix_window_f32(float* const* out, const float* const* rows, const float* alphas,
@@ -610,11 +563,8 @@ extern "C" int cfa_mix_population_tf1_f32(float* const* out_ptrs, const float* c
     return fail(CFA_E_INVALID, "null population table");
   if (D > 65535) return fail(CFA_E_INVALID, "D=%d exceeds grid.y limit", D);
   const long long nvec = (long long)P / 4;
-  long long gx = (nvec + kBlock - 1) / kBlock;
-  const long long cap = ((long long)device_cus() * pop_wg_per_cu() + D - 1) / D;
-  if (gx > cap) gx = cap;
-  if (gx < 1) gx = 1;
-  population_tf1_kernel<<<dim3((unsigned)gx, (unsigned)D), kBlock, 0, (hipStream_t)stream>>>(
+  const unsigned gx = shared_grid_x((nvec + kBlock - 1) / kBlock, pop_wg_per_cu(), D);
+  population_tf1_kernel<<<dim3(gx, (unsigned)D), kBlock, 0, (hipStream_t)stream>>>(
       out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, nvec, (long long)P, cp);
   return check_launch("population_tf1");
 }
@@ -634,11 +584,7 @@ extern "C" int cfa_mix_population_f32(float* const* out_ptrs, const float* const
   // Buckets in a population are expected 16-byte aligned (allocator contract, checked by the
   // host layer); the body runs on float4, the <4-element tail in the first tile column.
   const long long nvec = (long long)P / 4;
-  long long gx = (nvec + 2LL * kBlock - 1) / (2LL * kBlock);
-  const long long cap = ((long long)device_cus() * pop_wg_per_cu() + D - 1) / D;
-  if (gx > cap) gx = cap;
-  if (gx < 1) gx = 1;
-  dim3 grid((unsigned)gx, (unsigned)D);
+  dim3 grid(shared_grid_x((nvec + 2LL * kBlock - 1) / (2LL * kBlock), pop_wg_per_cu(), D), (unsigned)D);
   if (rule == CFA_RULE_SEQUENTIAL)
     population_kernel<CFA_RULE_SEQUENTIAL><<<grid, kBlock, 0, st>>>(out_ptrs, src_ptrs, csr_ptr,
                                                                     csr_idx, csr_coef, nvec, (long long)P);
@@ -696,9 +642,7 @@ __global__ __launch_bounds__(kBlock) void ge_step_kernel(GeStepArgs a, long long
     f4 w = ld4<false>(a.src[a.idx[e0]], i);
     for (int e = e0 + 1; e < e1; ++e) {  // stage 1: sequential rule
       const f4 x = ld4<false>(a.src[a.idx[e]], i);
-      f4 t = x - w;
-      t = a.coef[e] * t;
-      w = w + t;
+      w = seq_step(w, x, a.coef[e]);
     }
     f4 lr;
 #pragma unroll
@@ -716,11 +660,7 @@ __global__ __launch_bounds__(kBlock) void ge_step_kernel(GeStepArgs a, long long
   if (blockIdx.x == 0) {  // the < 4-element tail
     for (long long i = nvec * 4 + threadIdx.x; i < P; i += kBlock) {
       float w = a.src[a.idx[e0]][i];
-      for (int e = e0 + 1; e < e1; ++e) {
-        float t = a.src[a.idx[e]][i] - w;
-        t = a.coef[e] * t;
-        w = w + t;
-      }
+      for (int e = e0 + 1; e < e1; ++e) w = seq_step(w, a.src[a.idx[e]][i], a.coef[e]);
       const float lr = ge_lr(a, i);
       for (int e = e0 + 1; e < e1; ++e) {
         const float g = a.grad[e] ? a.grad[e][i] : 0.f;
@@ -757,11 +697,7 @@ extern "C" int cfa_ge_population_step_f32(float* const* out_ptrs, const float* c
                reduce_ws, reduce_out, reduce_M, reduce_splits};
   // buckets are 16-byte aligned (allocator contract, checked by the host layer)
   const long long nvec = (long long)P / 4;
-  long long gx = (nvec + kBlock - 1) / kBlock;
-  const long long cap = ((long long)device_cus() * pop_wg_per_cu() + D + reduce_M - 1) / (D + reduce_M);
-  if (gx > cap) gx = cap;
-  if (gx < 1) gx = 1;
-  dim3 grid((unsigned)gx, (unsigned)(D + reduce_M));
+  dim3 grid(shared_grid_x((nvec + kBlock - 1) / kBlock, pop_wg_per_cu(), D + reduce_M), (unsigned)(D + reduce_M));
   ge_step_kernel<<<grid, kBlock, 0, static_cast<hipStream_t>(stream)>>>(a, nvec, (long long)P);
   return check_launch("ge_step_kernel");
 }

@@ -233,8 +233,7 @@ class RingPopulationShard:
         # run on any stream, so the fill is finished here, on the host, before the shard is used
         self._slide_alphas = None
         if self.device.type == "cuda" and fused is not False and not window_batch:
-            self._slide_alphas = torch.full((plan.L,), 1.0 / (plan.K + 1), dtype=torch.float32, device=self.device)
-            torch.cuda.current_stream(self.device).synchronize()
+            self._fill_slide_alphas()
         if stacks is not None:
             for t in stacks:
                 same_dev = t.device.type == self.device.type and (self.device.index is None
@@ -287,6 +286,11 @@ class RingPopulationShard:
                 g = plan.first + i
                 st = [stage_of[self.plan.locate(j)] for j in plan.neighbours(g) if self.plan.locate(j)[0] != "local"]
                 self._ready[i] = max(st) if st else -1
+
+    def _fill_slide_alphas(self) -> None:
+        p = self.plan
+        self._slide_alphas = torch.full((p.L,), 1.0 / (p.K + 1), dtype=torch.float32, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()
 
     def _direct_route(self):
         """One-stage, direct-only plan: the grouped exchange of round 1 (every halo bucket one
@@ -399,35 +403,24 @@ class RingPopulationShard:
         """One cfa_mix_ring_slide_f32 call over consecutive local devices ``run``."""
         p = self.plan
         if self._slide_alphas is None:  # ``fused`` switched on after construction: as in __init__
-            self._slide_alphas = torch.full((p.L,), 1.0 / (p.K + 1), dtype=torch.float32, device=self.device)
-            torch.cuda.current_stream(self.device).synchronize()
+            self._fill_slide_alphas()
         self.engine.ring_slide(self.mixed, self.models, self._slide_alphas[:len(run)], run[0], len(run),
                                p.hl, p.hr, stream)
 
     def _mix_set(self, devices: List[int], stream, timer=None, between=None) -> None:
         """Mix ``devices`` on ``stream``; ``between()`` (optional) after each launch (the host
         lane's non-blocking pump, so an H2D whose chunk has arrived is enqueued at once)."""
+        one = lambda run, s: self.mix_device(run[0], s)
         if self.window_batch:
-            for run in self.window_passes(devices):
-                if timer:
-                    timer(run[0], True)
-                self.mix_window(run, stream)
-                if timer:
-                    timer(run[-1], False)
-                if between:
-                    between()
-            return
-        if self.fuses():
-            runs = self.mix_runs(devices)
+            launches = [(run, self.mix_window) for run in self.window_passes(devices)]
+        elif self.fuses():
+            launches = [(run, self.mix_run if fused else one) for run, fused in self.mix_runs(devices)]
         else:
-            runs = [([i], False) for i in devices]
-        for run, fused in runs:
+            launches = [([i], one) for i in devices]
+        for run, launch in launches:
             if timer:
                 timer(run[0], True)
-            if fused:
-                self.mix_run(run, stream)
-            else:
-                self.mix_device(run[0], stream)
+            launch(run, stream)
             if timer:
                 timer(run[-1], False)
             if between:
