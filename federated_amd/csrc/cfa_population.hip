@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "cfa_internal.h"
+#include "cfa_slide_shape.h"
 
 // Resident workgroups per CU across a whole population launch (all devices together). 8 by
 // default; CFA_POP_WG_PER_CU overrides it per call (read at each launch, so one process can
@@ -263,14 +264,15 @@ __global__ __launch_bounds__(kBlock) void ring_round_kernel(RingArgs ra, long lo
 
 // ------------------------------------------------------------------------------------------
 // Sliding ring round (cfa_mix_ring_slide_f32): every row of a run of consecutive ring devices is
-// read ONCE and every output written once. A workgroup owns a column tile of kBlock float4 and a
-// segment (blockIdx.y) of `seg` consecutive devices. It walks the segment's row stream
-// (rows d0-HL .. d0+len-1+HR, mod `rows`) through a ring of W + PF register slots, W = HL+HR+1:
-// device m of the segment folds stream rows m .. m+W-1 (its local row is m+HL) while the loads of
-// rows m+W .. m+W-1+PF are in flight. The device loop is unrolled W + PF times, so stream row q
-// always sits in slot q mod (W + PF) and every register index is static. A segment re-reads HL+HR
-// halo rows: a call reads count + segments * (HL+HR) rows. The fold is the window pass's
-// (ring_fold), on the slots the window's rows sit in.
+// read ONCE and every output written once. A workgroup owns a column tile of kBlock * U float4
+// (lane x holds vectors base + v * kBlock, v < U, so each wave instruction is a contiguous 1 KB)
+// and a segment (blockIdx.y) of `seg` consecutive devices. It walks the segment's row stream
+// (rows d0-HL .. d0+len-1+HR, mod `rows`) through a ring of W + PF register slots of U float4,
+// W = HL+HR+1: device m of the segment folds stream rows m .. m+W-1 (its local row is m+HL) while
+// the loads of rows m+W .. m+W-1+PF are in flight. The device loop is unrolled W + PF times, so
+// stream row q always sits in slot q mod (W + PF) and every register index is static. A segment
+// re-reads HL+HR halo rows: a call reads count + segments * (HL+HR) rows. The fold is the window
+// pass's (ring_fold), on the slots the window's rows sit in, per vector.
 // ------------------------------------------------------------------------------------------
 struct SlideArgs {
   const float* in;
@@ -281,10 +283,11 @@ struct SlideArgs {
   int rows, first, count, seg;     // seg: devices per segment
 };
 
-template <int HL, int HR, int PF, bool SC1>
+template <int HL, int HR, int PF, int U, bool SC1>
 __global__ __launch_bounds__(kBlock) void ring_slide_kernel(SlideArgs sa, long long nvec) {
   constexpr int W = HL + HR + 1;
   constexpr int RS = W + PF;
+  constexpr long long kTile = (long long)kBlock * U;
   const int n0 = (int)blockIdx.y * sa.seg;  // first device of the segment, relative to sa.first
   const int len = min(sa.seg, sa.count - n0);
   const int total = len + HL + HR;  // rows of the segment's stream
@@ -296,36 +299,51 @@ __global__ __launch_bounds__(kBlock) void ring_slide_kernel(SlideArgs sa, long l
   float* const out = sa.out + sa.off;
   const float* const in_end = in + (long long)sa.rows * sa.in_pitch;
   float* const out_end = out + (long long)sa.rows * sa.out_pitch;
-  for (long long t = blockIdx.x; t * kBlock < nvec; t += gridDim.x) {
-    const long long i = t * kBlock + threadIdx.x;
-    if (i >= nvec) continue;
-    const unsigned voff = (unsigned)(i * 16);  // a chunk is at most kMaxChunkVec float4: below 2^31
+  for (long long t = blockIdx.x; t * kTile < nvec; t += gridDim.x) {
+    const long long i = t * kTile + threadIdx.x;
+    if (i >= nvec) continue;  // the stripes ascend: a lane without its first vector has none
+    // Byte offsets of the lane's vectors (a chunk is at most kMaxChunkVec float4: below 2^31). In
+    // the last tile a stripe may lie partly or wholly past nvec: such a vector loads the lane's
+    // first vector again (in bounds, so the loads need no branch) and is never stored.
+    bool ok[U];
+    unsigned voff[U];
+#pragma unroll
+    for (int v = 0; v < U; ++v) {
+      ok[v] = i + (long long)v * kBlock < nvec;
+      voff[v] = (unsigned)((ok[v] ? i + (long long)v * kBlock : i) * 16);
+    }
     const float* rp = in + (long long)g0 * sa.in_pitch;  // next row of the stream to load
     float* op = out + (long long)o0 * sa.out_pitch;      // next output row
-    f4 r[RS];
+    f4 r[RS][U];
+    auto load_row = [&](f4(&slot)[U]) {  // all U loads of the stream's next row
+#pragma unroll
+      for (int v = 0; v < U; ++v)
+        slot[v] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(reinterpret_cast<const char*>(rp) + voff[v]));
+      rp += sa.in_pitch;
+      if (rp == in_end) rp = in;
+    };
 #pragma unroll
     for (int q = 0; q < RS - 1; ++q)
-      if (q < total) {
-        r[q] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(reinterpret_cast<const char*>(rp) + voff));
-        rp += sa.in_pitch;
-        if (rp == in_end) rp = in;
-      }
+      if (q < total) load_row(r[q]);
     for (int n = 0; n < len; n += RS) {
 #pragma unroll
       for (int u = 0; u < RS; ++u) {
         const int m = n + u;
         if (m < len) {
-          if (m + RS - 1 < total) {  // stream row m+W-1+PF: into the slot row m-1 has left
-            r[(u + RS - 1) % RS] =
-                __builtin_nontemporal_load(reinterpret_cast<const f4*>(reinterpret_cast<const char*>(rp) + voff));
-            rp += sa.in_pitch;
-            if (rp == in_end) rp = in;
-          }
-          const f4 acc = ring_fold<HL, HR>([&](int j) { return r[(u + j) % RS]; }, sa.alphas[n0 + m]);
-          if constexpr (SC1)
-            st16_buf<kStoreSc1>(out_rsrc(op, (unsigned)(nvec * 16)), i, acc);
-          else
-            __builtin_nontemporal_store(acc, reinterpret_cast<f4*>(reinterpret_cast<char*>(op) + voff));
+          // stream row m+W-1+PF: into the slot row m-1 has left
+          if (m + RS - 1 < total) load_row(r[(u + RS - 1) % RS]);
+          const float a = sa.alphas[n0 + m];
+          f4 acc[U];
+#pragma unroll
+          for (int v = 0; v < U; ++v) acc[v] = ring_fold<HL, HR>([&](int j) { return r[(u + j) % RS][v]; }, a);
+#pragma unroll
+          for (int v = 0; v < U; ++v)
+            if (ok[v]) {
+              if constexpr (SC1)
+                st16_buf<kStoreSc1>(out_rsrc(op, (unsigned)(nvec * 16)), i + (long long)v * kBlock, acc[v]);
+              else
+                __builtin_nontemporal_store(acc[v], reinterpret_cast<f4*>(reinterpret_cast<char*>(op) + voff[v]));
+            }
           op += sa.out_pitch;
           if (op == out_end) op = out;
         }
@@ -416,23 +434,31 @@ void launch_ring_round(const RingArgs& ra, long long nvec, hipStream_t st) {
 
 // Launch shape of the sliding ring round. The environment overrides are read at each launch, so
 // one process can compare shapes on the same buffers (tools/probe/ring_slide.py); results are
-// identical for every shape.
-struct SlideTune {
-  int segments, wg_per_cu, pf, sc1;
-};
+// identical for every shape. SlideTune and its default are in cfa_slide_shape.h; here u = 0 stands
+// for the tuned width, stepped down where a short row would leave workgroups without a tile
+// (slide_pick_u), and CFA_SLIDE_U = 1, 2 or 4 for exactly that width.
+static_assert(kSlideBlock == kBlock, "cfa_slide_shape.h counts tiles of kBlock lanes");
 static SlideTune slide_tune() {
-  const SlideTune d{1, 4, 2, 0};  // tools/probe/ring_slide.py sweep, profiles/r07_ring_slide_sweep.jsonl
+  const SlideTune d = kSlideDefault;
   SlideTune t{env_int("CFA_SLIDE_SEGMENTS", d.segments), env_int("CFA_SLIDE_WG_PER_CU", d.wg_per_cu),
-              env_int("CFA_SLIDE_PF", d.pf), env_int("CFA_SLIDE_SC1", d.sc1) ? 1 : 0};
+              env_int("CFA_SLIDE_PF", d.pf), env_int("CFA_SLIDE_SC1", d.sc1) ? 1 : 0, env_int("CFA_SLIDE_U", 0)};
   if (t.segments <= 0) t.segments = d.segments;
   if (t.wg_per_cu <= 0) t.wg_per_cu = d.wg_per_cu;
-  if (t.pf < 1 || t.pf > 4) t.pf = d.pf;
+  if (t.pf < 1 || t.pf > 2) t.pf = d.pf;
+  if (t.u != 1 && t.u != 2 && t.u != 4) t.u = 0;
   return t;
 }
-template <int HL, int HR, int PF>
-void launch_slide_pf(const SlideArgs& c, long long m, dim3 grid, bool sc1, hipStream_t st) {
-  if (sc1) ring_slide_kernel<HL, HR, PF, true><<<grid, kBlock, 0, st>>>(c, m);
-  else ring_slide_kernel<HL, HR, PF, false><<<grid, kBlock, 0, st>>>(c, m);
+template <int HL, int HR, int PF, int U>
+void launch_slide_shape(const SlideArgs& c, long long m, dim3 grid, bool sc1, hipStream_t st) {
+  if (sc1) ring_slide_kernel<HL, HR, PF, U, true><<<grid, kBlock, 0, st>>>(c, m);
+  else ring_slide_kernel<HL, HR, PF, U, false><<<grid, kBlock, 0, st>>>(c, m);
+}
+template <int HL, int HR, int U>
+void launch_slide_u(const SlideArgs& c, long long m, dim3 grid, const SlideTune& t, hipStream_t st) {
+  switch (t.pf) {
+    case 1: launch_slide_shape<HL, HR, 1, U>(c, m, grid, t.sc1, st); break;
+    default: launch_slide_shape<HL, HR, 2, U>(c, m, grid, t.sc1, st); break;
+  }
 }
 template <int HL, int HR>
 void launch_ring_slide(const SlideArgs& sa, long long nvec, hipStream_t st) {
@@ -444,13 +470,13 @@ void launch_ring_slide(const SlideArgs& sa, long long nvec, hipStream_t st) {
   const unsigned gy = (unsigned)((sa.count + c.seg - 1) / c.seg);  // no empty segment
   for_each_chunk(nvec, [&](long long done, long long m) {
     c.off = done * 4;
+    const int u = t.u ? t.u : slide_pick_u(m, kSlideDefault.u, device_cus(), t.wg_per_cu);
     // the launch's workgroups over all segments: about wg_per_cu per CU in all
-    const dim3 grid(shared_grid_x((m + kBlock - 1) / kBlock, t.wg_per_cu, gy), gy);
-    switch (t.pf) {
-      case 1: launch_slide_pf<HL, HR, 1>(c, m, grid, t.sc1, st); break;
-      case 3: launch_slide_pf<HL, HR, 3>(c, m, grid, t.sc1, st); break;
-      case 4: launch_slide_pf<HL, HR, 4>(c, m, grid, t.sc1, st); break;
-      default: launch_slide_pf<HL, HR, 2>(c, m, grid, t.sc1, st); break;
+    const dim3 grid(shared_grid_x(slide_tiles(m, u), t.wg_per_cu, gy), gy);
+    switch (u) {
+      case 4: launch_slide_u<HL, HR, 4>(c, m, grid, t, st); break;
+      case 2: launch_slide_u<HL, HR, 2>(c, m, grid, t, st); break;
+      default: launch_slide_u<HL, HR, 1>(c, m, grid, t, st); break;
     }
   });
 }

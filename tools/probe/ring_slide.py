@@ -1,16 +1,16 @@
 #!/usr/bin/env python3
 """The sliding ring round (cfa_mix_ring_slide_f32) on the bench's population (128 devices x 25M
 fp32, K = 8 by default). The kernel reads its launch shape from the environment at every launch
-(CFA_SLIDE_SEGMENTS, CFA_SLIDE_PF, CFA_SLIDE_WG_PER_CU, CFA_SLIDE_SC1; results identical), so one
-process compares shapes on the same stacks. One JSON line per record.
+(CFA_SLIDE_SEGMENTS, CFA_SLIDE_PF, CFA_SLIDE_WG_PER_CU, CFA_SLIDE_SC1, CFA_SLIDE_U; results
+identical), so one process compares shapes on the same stacks. One JSON line per record.
 
   ring_slide.py sweep            every shape, interleaved over passes: median us per round
   ring_slide.py ab [reps]        the slide round (shape from the environment) alternated with
                                  cfa_mix_ring_round_f32, `reps` (10) times each
   ring_slide.py once [launches]  only slide launches (for rocprofv3 --pmc runs, one counter per run)
 
-Environment: RS_DEVICES, RS_P, RS_H (window half-width), RS_SEGMENTS / RS_PF / RS_WG / RS_SC1
-(comma lists of the sweep), RS_PASSES."""
+Environment: RS_DEVICES, RS_P, RS_H (window half-width), RS_SEGMENTS / RS_PF / RS_WG / RS_SC1 /
+RS_U (comma lists of the sweep; RS_U: float4 per lane and row, 1, 2 or 4), RS_PASSES."""
 import itertools
 import json
 import os
@@ -50,7 +50,8 @@ def main():
 
     def slide(shape=None):
         if shape is not None:
-            for key, v in zip(("CFA_SLIDE_SEGMENTS", "CFA_SLIDE_PF", "CFA_SLIDE_WG_PER_CU", "CFA_SLIDE_SC1"), shape):
+            for key, v in zip(("CFA_SLIDE_SEGMENTS", "CFA_SLIDE_PF", "CFA_SLIDE_WG_PER_CU", "CFA_SLIDE_SC1",
+                               "CFA_SLIDE_U"), shape):
                 os.environ[key] = str(v)
         eng.ring_slide(out, models, alphas, 0, D, H, H)
 
@@ -79,8 +80,8 @@ def main():
                                       slide_env={k: v for k, v in os.environ.items() if k.startswith("CFA_SLIDE_")})),
                       flush=True)
     else:
-        shapes = list(itertools.product(ints("RS_SEGMENTS", "1,2,4,8"), ints("RS_PF", "1,2,3,4"),
-                                        ints("RS_WG", "4,8,16"), ints("RS_SC1", "0,1")))
+        shapes = list(itertools.product(ints("RS_SEGMENTS", "1"), ints("RS_PF", "1,2"),
+                                        ints("RS_WG", "1,2,4"), ints("RS_SC1", "0"), ints("RS_U", "1,2,4")))
         times = {s: [] for s in shapes}
         for _ in range(int(os.environ.get("RS_PASSES", "3"))):
             for s in shapes:
@@ -88,9 +89,9 @@ def main():
         for s in sorted(shapes, key=lambda s: statistics.median(times[s])):
             us = statistics.median(times[s])
             mb = moved_bytes(s[0])
-            print(json.dumps(dict(base, segments=s[0], pf=s[1], wg_per_cu=s[2], sc1=s[3], us_per_round=round(us, 2),
-                                  spread_us=round(max(times[s]) - min(times[s]), 2), moved_bytes=mb,
-                                  moved_frac_of_peak=round(mb / (us * 1e-6) / PEAK, 4))), flush=True)
+            print(json.dumps(dict(base, segments=s[0], pf=s[1], wg_per_cu=s[2], sc1=s[3], u=s[4],
+                                  us_per_round=round(us, 2), spread_us=round(max(times[s]) - min(times[s]), 2),
+                                  moved_bytes=mb, moved_frac_of_peak=round(mb / (us * 1e-6) / PEAK, 4))), flush=True)
 
 
 if __name__ == "__main__":
