@@ -555,21 +555,6 @@ __global__ __launch_bounds__(kGradBlock) void grad_2nn_kernel(const float* __res
   }
 }
 
-// Dynamic LDS for one workgroup: up to 64 KiB by default; above that the kernel's limit is
-// raised to the device's (160 KiB on gfx950) when the runtime allows it.
-int device_lds_max() {  // per device, cached after the first query
-  static int cache[64] = {0};
-  int dev = 0, v = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 65536;
-  if (dev >= 0 && dev < 64) {
-    const int c = __atomic_load_n(&cache[dev], __ATOMIC_RELAXED);
-    if (c > 0) return c;
-  }
-  if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || v <= 0) v = 65536;
-  if (dev >= 0 && dev < 64) __atomic_store_n(&cache[dev], v, __ATOMIC_RELAXED);
-  return v;
-}
-
 // Raise a kernel's dynamic-LDS limit to `bytes` once per (kernel, device); false if refused.
 bool raise_lds_limit(const void* kernel, int bytes) {
   static const void* keys[8] = {nullptr};
@@ -629,11 +614,8 @@ __global__ __launch_bounds__(kBlock) void reduce_splits_kernel(const float* __re
                                                                float* __restrict__ grads, int Sp,
                                                                long long P) {
   const long long m = blockIdx.y;
-  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < P; i += (long long)gridDim.x * kBlock) {
-    float s = ws[(m * Sp) * P + i];
-    for (int sp = 1; sp < Sp; ++sp) s += ws[(m * Sp + sp) * P + i];
-    grads[m * P + i] = s;
-  }
+  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < P; i += (long long)gridDim.x * kBlock)
+    grads[m * P + i] = split_sum(ws + (m * Sp) * P + i, Sp, P);
 }
 
 int launch_reduce_splits(const float* ws, float* grads, int M, int Sp, long long P, hipStream_t st) {
@@ -660,6 +642,32 @@ int batch_split(int M, int B, long long P) {
 // Workspace of a split launch: the M * Sp partial buckets.
 size_t split_workspace_elems(int M, int Sp, long long P) { return (size_t)M * Sp * (size_t)P; }
 
+// What the two gradient launchers share once d holds the graph's dimensions (B, P): the batch
+// split (one workgroup per evaluation when no workspace holds the partials), the LDS chunk plan
+// of a workgroup's samples, launch(grid, lds_bytes, part) of `kern` into the partial buckets, and
+// the reduction of the splits into `grads`.
+template <typename Dims, typename Launch>
+int launch_grad_split(const char* fn, const char* what, const void* kern, Dims& d, long long lds_fixed,
+                      long long lds_per_sample, float* grads, float* ws, size_t ws_elems, int M, hipStream_t st,
+                      Launch&& launch) {
+  int Sp = batch_split(M, d.B, d.P);
+  if (!grads) {  // partials only: [M][Sp][P] into the workspace, summed by the caller
+    if (ws_elems < split_workspace_elems(M, Sp, d.P))
+      return fail(CFA_E_INVALID, "%s: partials-only launch needs %zu workspace floats", fn,
+                  split_workspace_elems(M, Sp, d.P));
+  } else if (!ws || ws_elems < split_workspace_elems(M, Sp, d.P)) {
+    Sp = 1;
+  }
+  d.Bs = (d.B + Sp - 1) / Sp;
+  // LDS for the samples one workgroup takes (its split), not the whole batch
+  long long bytes = 0;
+  d.Bc = plan_chunk(kern, lds_fixed, lds_per_sample, d.Bs, &bytes);
+  if (d.Bc < 1) return fail(CFA_E_UNSUPPORTED, "%s: one sample does not fit the workgroup's LDS", fn);
+  launch(dim3((unsigned)M, (unsigned)Sp), (size_t)bytes, (Sp > 1 || !grads) ? ws : grads);
+  if (int rc = check_launch(what)) return rc;
+  return (Sp > 1 && grads) ? launch_reduce_splits(ws, grads, M, Sp, d.P, st) : CFA_OK;
+}
+
 int launch_grad_cnn(const char* fn, const float* x, const float* y, int B, int L, int classes, int filter,
                     int number, int stride, const float* models, const int* mrow, const int* drow,
                     float* grads, float* ws, size_t ws_elems, int M, void* stream) {
@@ -677,32 +685,18 @@ int launch_grad_cnn(const char* fn, const float* x, const float* y, int B, int L
   d.pl = same_left(L, filter, stride);
   d.ql = same_left(d.L1, stride, stride);
   d.P = (long long)filter * number + number + (long long)d.L2 * number * classes + classes;
-  long long bytes = 0;
   // the CFA-GE CNN's geometry (filter 16, stride 5: federated_sample_CNN_CFA-GE.py:36-39) gets
   // the unrolled kernel
   const bool fast = filter == 16 && stride == 5;
   const void* kern = fast ? (const void*)grad_cnn_kernel<16, 5> : (const void*)grad_cnn_kernel<0, 0>;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  int Sp = batch_split(M, B, d.P);
-  if (!grads) {  // partials only: [M][Sp][P] into the workspace, summed by the caller
-    if (ws_elems < split_workspace_elems(M, Sp, d.P))
-      return fail(CFA_E_INVALID, "%s: partials-only launch needs %zu workspace floats", fn,
-                  split_workspace_elems(M, Sp, d.P));
-  } else if (!ws || ws_elems < split_workspace_elems(M, Sp, d.P)) {
-    Sp = 1;
-  }
-  d.Bs = (B + Sp - 1) / Sp;
-  // LDS for the samples one workgroup takes (its split), not the whole batch
-  d.Bc = plan_chunk(kern, cnn_lds_fixed(d), cnn_lds_per_sample(d), d.Bs, &bytes);
-  if (d.Bc < 1) return fail(CFA_E_UNSUPPORTED, "%s: one sample does not fit the workgroup's LDS", fn);
-  float* part = (Sp > 1 || !grads) ? ws : grads;
-  const dim3 grid((unsigned)M, (unsigned)Sp);
-  if (fast)
-    grad_cnn_kernel<16, 5><<<grid, kGradBlock, (size_t)bytes, st>>>(x, y, models, mrow, drow, part, d);
-  else
-    grad_cnn_kernel<0, 0><<<grid, kGradBlock, (size_t)bytes, st>>>(x, y, models, mrow, drow, part, d);
-  if (int rc = check_launch("grad_cnn_kernel")) return rc;
-  return (Sp > 1 && grads) ? launch_reduce_splits(ws, grads, M, Sp, d.P, st) : CFA_OK;
+  return launch_grad_split(fn, "grad_cnn_kernel", kern, d, cnn_lds_fixed(d), cnn_lds_per_sample(d), grads, ws,
+                           ws_elems, M, st, [&](dim3 grid, size_t bytes, float* part) {
+    if (fast)
+      grad_cnn_kernel<16, 5><<<grid, kGradBlock, bytes, st>>>(x, y, models, mrow, drow, part, d);
+    else
+      grad_cnn_kernel<0, 0><<<grid, kGradBlock, bytes, st>>>(x, y, models, mrow, drow, part, d);
+  });
 }
 
 int launch_grad_2nn(const char* fn, const float* x, const float* y, int B, int L, int hidden, int classes,
@@ -718,25 +712,12 @@ int launch_grad_2nn(const char* fn, const float* x, const float* y, int B, int L
   d.SW = softmax_width(classes);
   d.G = (L + kSpan - 1) / kSpan;
   d.P = (long long)L * hidden + hidden + (long long)hidden * classes + classes;
-  long long bytes = 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  int Sp = batch_split(M, B, d.P);
-  if (!grads) {  // partials only: [M][Sp][P] into the workspace, summed by the caller
-    if (ws_elems < split_workspace_elems(M, Sp, d.P))
-      return fail(CFA_E_INVALID, "%s: partials-only launch needs %zu workspace floats", fn,
-                  split_workspace_elems(M, Sp, d.P));
-  } else if (!ws || ws_elems < split_workspace_elems(M, Sp, d.P)) {
-    Sp = 1;
-  }
-  d.Bs = (B + Sp - 1) / Sp;
-  // LDS for the samples one workgroup takes (its split), not the whole batch
-  d.Bc = plan_chunk((const void*)grad_2nn_kernel, nn_lds_fixed(d), nn_lds_per_sample(d), d.Bs, &bytes);
-  if (d.Bc < 1) return fail(CFA_E_UNSUPPORTED, "%s: one sample does not fit the workgroup's LDS", fn);
-  float* part = (Sp > 1 || !grads) ? ws : grads;
-  grad_2nn_kernel<<<dim3((unsigned)M, (unsigned)Sp), kGradBlock, (size_t)bytes, st>>>(x, y, models, mrow, drow, part,
-                                                                                       d);
-  if (int rc = check_launch("grad_2nn_kernel")) return rc;
-  return (Sp > 1 && grads) ? launch_reduce_splits(ws, grads, M, Sp, d.P, st) : CFA_OK;
+  return launch_grad_split(fn, "grad_2nn_kernel", (const void*)grad_2nn_kernel, d, nn_lds_fixed(d),
+                           nn_lds_per_sample(d), grads, ws, ws_elems, M, st,
+                           [&](dim3 grid, size_t bytes, float* part) {
+    grad_2nn_kernel<<<grid, kGradBlock, bytes, st>>>(x, y, models, mrow, drow, part, d);
+  });
 }
 
 }  // namespace

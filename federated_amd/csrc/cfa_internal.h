@@ -1,8 +1,12 @@
 // cfa_internal.h — shared internals of libcfa's translation units (not installed, not an ABI).
 //
-// Device helpers for gfx950 (MI355X / CDNA4): the float4 streaming loads and stores, the fold of
-// the sequential / linear / FedAvg rules, the compression epilogue, the launch-shape defaults,
-// and the thread-local error reporting behind cfa_last_error(). Every .hip file of the library
+// Device helpers for gfx950 (MI355X / CDNA4): the float4 streaming loads and stores, ONE
+// definition of each mixing rule's step (seq_step, div_step, lin_step, tf1_first / tf1_step,
+// div_step_f64, mewma_step, mewma_step_f64, split_sum) that every kernel of the library calls,
+// the fold of the sequential / linear / FedAvg rules, the tile walk (TileWalk) and the fan-in
+// dispatch (dispatch_fanin) of the streaming kernels, the compression epilogue, and the
+// thread-local error reporting behind cfa_last_error(). The host-only launch rules (shape bands,
+// bucket split, passes) are in cfa_mix_shape.h. Every .hip file of the library
 // is compiled with -ffp-contract=off: CFA_RULE_SEQUENTIAL evaluates t = x - w; t = a * t;
 // w = w + t exactly as fp32 numpy does (three roundings), which makes the TF2 path
 // bit-identical to the reference; CFA_RULE_LINEAR uses explicit fmaf.
@@ -16,8 +20,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
+#include <utility>
 
 #include "cfa_engine.h"
+#include "cfa_mix_shape.h"
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef unsigned u4v __attribute__((ext_vector_type(4)));
@@ -67,38 +74,6 @@ constexpr int kBlock = 256;  // 4 waves of 64 lanes
 // kernel takes its own shape (mix_auto_shape), every other kernel kDefaultBlocks.
 constexpr int kDefaultBlocks = 2;
 constexpr int kAutoBlocks = -1;
-static int norm_vec(int v) { return v >= 4 ? 4 : (v >= 2 ? 2 : (v == 1 ? 1 : 0)); }
-static int auto_vec(int n) { return (n + 1) * 4 <= 40 ? 4 : ((n + 1) * 2 <= 40 ? 2 : 1); }
-// The streaming mix's own default (round 2, tools/probe/tune_placed.py on placement-calibrated
-// stacks, profiles/r02_tune_placed.jsonl: every shape of 1-4 workgroups per CU x 1/2/4 float4 per
-// lane at K = 2/4/8/12 on two boxes): one workgroup per CU (one wave per SIMD) at every fan-in,
-// two float4 per lane except for 3-5 neighbours, where one is best. Sequential rule only.
-static int mix_auto_vec(int n) { return (n >= 3 && n <= 5) ? 1 : ((n + 1) * 2 <= 40 ? 2 : 1); }
-// ... for buckets of 8M elements and more. Shorter mixes need more loads in flight than one
-// wave per SIMD issues (round 3, tools/probe/slice_shape.py on placement-calibrated populations,
-// P = 0.5M-25M; profiles/r03_slice_shape_k{4,8}.jsonl for the sweep, r03_ab_shape.jsonl for two
-// rounds of A/B against the one-workgroup shape at K = 2/4/8/16). Four workgroups per CU:
-//   - with one float4 per lane from 512K to 1.5M elements (1M: +2-13% in 3 of 4 A/B pairs);
-//   - with four float4 from 1.5M to 8M (3.125M, the N = 8 bench rank's slice: +6-13% on ring
-//     windows, +7% on rows no two consecutive mixes share; 6.25M: +1-5%);
-//   - with two for 10-16 neighbours from 1.5M to 3M (+3-5%; neutral to -2% above).
-// Below 512K elements (e.g. the drop-in pipeline's 128K chunks read over PCIe; at 500K the A/B
-// pairs split both ways at K = 4 and 16) the shape is unchanged.
-static void mix_auto_shape(int n, long long nvec, int& blocks_per_cu, int& vec) {
-  const long long elems = nvec * 4;
-  const bool narrow = (n + 1) * 4 <= 40;
-  blocks_per_cu = 4;
-  if (elems >= (1LL << 19) && elems < (3LL << 19)) {
-    vec = 1;
-  } else if (elems >= (3LL << 19) && elems < (8LL << 20) && narrow) {
-    vec = 4;
-  } else if (elems >= (3LL << 19) && elems < (3LL << 20) && !narrow) {
-    vec = 2;
-  } else {
-    blocks_per_cu = 1;
-    vec = mix_auto_vec(n);
-  }
-}
 static cfa_launch_t read_tune() {
   cfa_launch_t t{kAutoBlocks, 0, 1};
   if (const char* s = getenv("CFA_BLOCKS_PER_CU")) {
@@ -124,24 +99,31 @@ static const cfa_launch_t& tune() {
 
 }  // namespace
 
-// Per-device CU count, cached after the first query. An inline function with external linkage,
-// so every translation unit shares one cache; cfa_device_prepare() fills it before any launch
-// (the launch path then only reads it, which keeps hipGraph capture free of device queries).
-inline int device_cus() {
-  static int cache[64] = {0};
+// Per-device attributes, cached after the first query: the CU count and the LDS a workgroup may
+// take. Inline functions with external linkage, so every translation unit shares one cache;
+// cfa_device_prepare() fills it before any launch (the launch path then only reads it, which keeps
+// hipGraph capture free of device queries). A failed query gives `fallback`, and caches it when
+// `keep_fallback` (the LDS size; a failed CU-count query is asked again).
+inline int device_attr(int slot, hipDeviceAttribute_t attr, int fallback, bool keep_fallback) {
+  static int cache[2][64] = {{0}};
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 256;
+  if (hipGetDevice(&dev) != hipSuccess) return fallback;
   if (dev >= 0 && dev < 64) {
-    const int c = __atomic_load_n(&cache[dev], __ATOMIC_RELAXED);
+    const int c = __atomic_load_n(&cache[slot][dev], __ATOMIC_RELAXED);
     if (c > 0) return c;
   }
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      cus <= 0)
-    return 256;
-  if (dev >= 0 && dev < 64) __atomic_store_n(&cache[dev], cus, __ATOMIC_RELAXED);
-  return cus;
+  int v = 0;
+  if (hipDeviceGetAttribute(&v, attr, dev) != hipSuccess || v <= 0) {
+    if (!keep_fallback) return fallback;
+    v = fallback;
+  }
+  if (dev >= 0 && dev < 64) __atomic_store_n(&cache[slot][dev], v, __ATOMIC_RELAXED);
+  return v;
 }
+inline int device_cus() { return device_attr(0, hipDeviceAttributeMultiprocessorCount, 256, false); }
+// Dynamic LDS for one workgroup: up to 64 KiB by default; above that a kernel's limit is raised
+// to the device's (160 KiB on gfx950) when the runtime allows it (cfa_grad.hip).
+inline int device_lds_max() { return device_attr(1, hipDeviceAttributeMaxSharedMemoryPerBlock, 65536, true); }
 
 // cfa_grad.hip: per-device LDS query and kernel LDS limits, done ahead of any capture.
 int grad_prepare_device();
@@ -257,6 +239,140 @@ __device__ __forceinline__ T seq_step(T acc, T x, float a) {
   return acc + t;  //        w + (...)
 }
 
+// One step of the FedAvg divisor rule: t = x - w; t = c * t; t = t / d; w = w + t, the division
+// between the multiply and the add (not seq_step). IEEE = false divides a float4 by the fp64
+// reciprocal rd (div4_rn, which records a subnormal quotient); IEEE = true is the IEEE division,
+// which the redo of such a tile and every scalar kernel take.
+template <bool IEEE, typename T>
+__device__ __forceinline__ T div_step(T w, T x, float c, float d, double rd, bool& subnormal) {
+  T t = x - w;  // numpy: (x - w)
+  t = c * t;    //        u * (...)
+  if constexpr (!IEEE) t = div4_rn(t, rd, subnormal);  // (...) / C, one fp64 multiply
+  else if constexpr (std::is_same_v<T, f4>) t = div4_ieee(t, d);
+  else t = t / d;
+  return w + t;
+}
+
+// One step of the linear closed form: w = fma(c, x, w) per element.
+template <typename T>
+__device__ __forceinline__ T lin_step(T w, T x, float c) {
+  if constexpr (std::is_same_v<T, float>) {
+    return fmaf(c, x, w);
+  } else {
+    w.x = fmaf(c, x.x, w.x);
+    w.y = fmaf(c, x.y, w.y);
+    w.z = fmaf(c, x.z, w.z);
+    w.w = fmaf(c, x.w, w.w);
+    return w;
+  }
+}
+
+// The TF1 chain under numpy 2 (cfa.py:66-76): the first subtraction x_1 - l of two fp32 arrays is
+// fp32 (tf1_first; l is the fp32 local, or an fp64 bucket that holds one), every later operation
+// fp64 with the fp64 coefficient a = eps * wf_j (tf1_step, which is also the fp64 folds'
+// sequential step on an fp64 x).
+template <typename L>
+__device__ __forceinline__ double tf1_first(L l, float x, double a) {
+  const float d = x - (float)l;       // fp32 - fp32 (both operands fp32)
+  return (double)l + a * (double)d;  // np.float64 * fp32 -> fp64; fp32 + fp64 -> fp64
+}
+template <typename X>
+__device__ __forceinline__ double tf1_step(double w, X x, double a) {
+  return w + a * ((double)x - w);
+}
+
+// Correctly rounded fp64 a / b (Markstein): q = RN(a * rb) with rb = RN(1/b) is within 1 ulp,
+// the remainder a - b q is exact (one fma), and RN(q + r * rb) is the correctly rounded quotient
+// when nothing under- or overflows; |a| in [2^-900, 2^900] and b in [2^-20, 2^20] guarantee
+// that, everything else takes the IEEE division. (The fp32 fold's one-multiply form, div4_rn
+// above, needs a format twice as wide; fp64 has none on the GPU.)
+__device__ __forceinline__ double ddiv_rn(double a, double b, double rb, bool fast) {
+  const double aa = __builtin_fabs(a);
+  if (fast && aa >= 0x1p-900 && aa <= 0x1p900) {
+    const double q = a * rb;
+    const double r = __builtin_fma(-q, b, a);
+    return __builtin_fma(r, rb, q);
+  }
+  return a / b;
+}
+// One fp64 step of the divisor rule, w + (a * (x - w)) / d: through ddiv_rn (r = RN(1 / d), `fast`
+// as there), or IEEE = true with the plain division.
+template <bool IEEE>
+__device__ __forceinline__ double div_step_f64(double w, double x, double a, double d, double r, bool fast) {
+  if constexpr (IEEE) return w + (a * (x - w)) / d;
+  else return w + ddiv_rn(a * (x - w), d, r, fast);
+}
+
+// One neighbour of the CFA-GE gradient step on a float4 or a float (cfa_ge_2stage.py:331-371,
+// :593-621): the MEWMA filter s = rho * g + (1 - rho) * s_old (g itself at init, s_old is then not
+// read), then W = W - lr * (filtered ? s : g); five separately rounded fp32 operations. Returns
+// the new state.
+template <typename T>
+__device__ __forceinline__ T mewma_step(T& W, T g, const T& s_old, float rho, float one_minus_rho, T lr, bool init,
+                                        bool filtered) {
+  T s;
+  if (init) {
+    s = g;
+  } else {
+    const T t1 = rho * g;  // numpy: rho*g + (1-rho)*s
+    const T t2 = one_minus_rho * s_old;
+    s = t1 + t2;
+  }
+  const T u = lr * (filtered ? s : g);
+  W = W - u;
+  return s;
+}
+
+// Python-float scalar times an array, in the array's dtype (numpy 2: the scalar is weak).
+__device__ __forceinline__ double scale(double c, double x, bool f32) {
+  return f32 ? (double)((float)c * (float)x) : c * x;
+}
+// The same step on the reference's TF1 arrays with numpy 2 promotion per operation:
+//   s_j = rho*g_j + (1-rho)*s_j (or g_j at init), stored in the state array's dtype;
+//   W   = W - lr*(filtered ? s_j : g_j).
+// Each product is computed in its array's dtype (s32 / g32: the state / gradient arrays are
+// fp32); a sum or difference is fp32 only when both operands are fp32, and W stays fp32 (w32) only
+// while every update it receives is fp32. Returns the new state.
+__device__ __forceinline__ double mewma_step_f64(double& W, bool& w32, double g, const double& s_old, double rho,
+                                                 double one_minus_rho, double lr, bool init, bool filtered,
+                                                 bool s32, bool g32) {
+  double s;
+  if (init) {
+    s = g;
+  } else {
+    const double t1 = scale(rho, g, g32);
+    const double t2 = scale(one_minus_rho, s_old, s32);
+    s = (g32 && s32) ? (double)((float)t1 + (float)t2) : t1 + t2;
+  }
+  if (s32) s = (double)(float)s;
+  const bool u32 = filtered ? s32 : g32;
+  const double t = scale(lr, filtered ? s : g, u32);
+  if (w32 && u32) {
+    W = (double)((float)W - (float)t);
+  } else {
+    W = W - t;
+    w32 = false;
+  }
+  return s;
+}
+
+// Sum of n partial values p[0], p[stride], ... in that order (deterministic): the batch splits of
+// a gradient evaluation.
+__device__ __forceinline__ float split_sum(const float* p, int n, long long stride) {
+  float s = p[0];
+  for (int sp = 1; sp < n; ++sp) s += p[(long long)sp * stride];
+  return s;
+}
+
+// The divisor fold of one float4 with either division: one loop body, instantiated twice by fold.
+template <int N, bool IEEE>
+__device__ __forceinline__ f4 fold_div(const f4 (&v)[N + 1], const Fanin& f, bool& subnormal) {
+  f4 w = v[0];
+#pragma unroll
+  for (int j = 1; j <= N; ++j) w = div_step<IEEE>(w, v[j], f.c[j], f.d[j], f.rd[j], subnormal);
+  return w;
+}
+
 template <int N, int RULE>
 __device__ __forceinline__ f4 fold(const f4 (&v)[N + 1], const Fanin& f) {
   if constexpr (RULE == CFA_RULE_SEQUENTIAL) {
@@ -265,37 +381,60 @@ __device__ __forceinline__ f4 fold(const f4 (&v)[N + 1], const Fanin& f) {
     for (int j = 1; j <= N; ++j) w = seq_step(w, v[j], f.c[j]);
     return w;
   } else if constexpr (RULE == CFA_RULE_SEQUENTIAL_DIV) {
-    f4 w = v[0];
     bool subnormal = false;
-#pragma unroll
-    for (int j = 1; j <= N; ++j) {
-      f4 t = v[j] - w;  // numpy: (x - w)
-      t = f.c[j] * t;   //        u * (...)
-      t = div4_rn(t, f.rd[j], subnormal);  // (...) / C, one fp64 multiply
-      w = w + t;
-    }
-    if (__builtin_expect(subnormal, 0)) {  // a subnormal quotient may be an exact tie: IEEE division
-      w = v[0];
-#pragma unroll
-      for (int j = 1; j <= N; ++j) {
-        f4 t = v[j] - w;
-        t = f.c[j] * t;
-        t = div4_ieee(t, f.d[j]);
-        w = w + t;
-      }
-    }
+    f4 w = fold_div<N, false>(v, f, subnormal);
+    // a subnormal quotient may be an exact tie: IEEE division
+    if (__builtin_expect(subnormal, 0)) w = fold_div<N, true>(v, f, subnormal);
     return w;
   } else {
     f4 w = f.c[0] * v[0];
 #pragma unroll
-    for (int j = 1; j <= N; ++j) {
-      w.x = fmaf(f.c[j], v[j].x, w.x);
-      w.y = fmaf(f.c[j], v[j].y, w.y);
-      w.z = fmaf(f.c[j], v[j].z, w.z);
-      w.w = fmaf(f.c[j], v[j].w, w.w);
-    }
+    for (int j = 1; j <= N; ++j) w = lin_step(w, v[j], f.c[j]);
     return w;
   }
+}
+
+// The walk of nvec vectors in tiles of kBlock * U by the workgroups of a launch:
+//   for (const long long base : tw.full_tiles())  every full tile this workgroup takes, grid-stride;
+//       base = the lane's first vector of the tile, its others follow at base + u * kBlock, no guards
+//   if (tw.owns_partial()) for (const long long i : tw.partial_tile())  the lane's vectors of the
+//       partial last tile, for the one workgroup that owns that tile (full % gridDim.x)
+// Each range is its own iterator (the end is a bound), so the loops compile to the plain ones.
+template <int U>
+struct TileWalk {
+  static constexpr long long kTile = (long long)kBlock * U;
+  long long nvec, full;  // full: the number of full tiles
+  __device__ explicit TileWalk(long long n) : nvec(n), full(n / kTile) {}
+  struct Tiles {
+    long long t, full;
+    __device__ Tiles begin() const { return *this; }
+    __device__ long long end() const { return full; }
+    __device__ bool operator!=(long long e) const { return t < e; }
+    __device__ void operator++() { t += gridDim.x; }
+    __device__ long long operator*() const { return t * kTile + threadIdx.x; }
+  };
+  struct Vectors {
+    long long i, nvec;
+    __device__ Vectors begin() const { return *this; }
+    __device__ long long end() const { return nvec; }
+    __device__ bool operator!=(long long e) const { return i < e; }
+    __device__ void operator++() { i += kBlock; }
+    __device__ long long operator*() const { return i; }
+  };
+  __device__ Tiles full_tiles() const { return {(long long)blockIdx.x, full}; }
+  __device__ bool owns_partial() const { return blockIdx.x == (unsigned)(full % gridDim.x); }
+  __device__ Vectors partial_tile() const { return {full * kTile + threadIdx.x, nvec}; }
+};
+
+// Run-time fan-in n to compile-time N: fn(std::integral_constant<int, N>{}) for the N in
+// LO..CFA_MAX_FANIN equal to n (nothing for an n outside).
+template <int LO, typename F, int... Is>
+inline void dispatch_fanin_seq(int n, F&& fn, std::integer_sequence<int, Is...>) {
+  ((n == LO + Is ? (void)fn(std::integral_constant<int, LO + Is>{}) : (void)0), ...);
+}
+template <int LO, typename F>
+inline void dispatch_fanin(int n, F&& fn) {
+  dispatch_fanin_seq<LO>(n, fn, std::make_integer_sequence<int, CFA_MAX_FANIN - LO + 1>{});
 }
 
 // Compression epilogue on one element (TF1/consensus/cfa_ongraphs.py:225-273), fp32 arrays.
@@ -309,12 +448,6 @@ __device__ __forceinline__ double np_sign(double x) {
 __device__ __forceinline__ float np_signf(float x) {
   return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : x);
 }
-struct CompressParams {
-  int mode;
-  double thr, rep;
-  long long cbegin, cend;  // element range the epilogue applies to
-  unsigned long long* kept;
-};
 __device__ __forceinline__ float compress_one(float y, float ref, const CompressParams& cp,
                                               unsigned& kept) {
   const float thr = (float)cp.thr, rep = (float)cp.rep;

@@ -1,7 +1,6 @@
 // cfa_mewma.hip — CFA-GE gradient-bucket update on fp32 buckets (MEWMA filter + SGD step with the
-// neighbours' gradients), TF1/consensus/cfa_ge_2stage.py:329-371 and :593-621.
-#include <utility>
-
+// neighbours' gradients), TF1/consensus/cfa_ge_2stage.py:329-371 and :593-621. The step itself is
+// mewma_step (cfa_internal.h), shared with the CFA-GE population step.
 #include "cfa_internal.h"
 
 namespace {
@@ -38,24 +37,14 @@ __global__ __launch_bounds__(kBlock) void mewma_vec_kernel(MewmaArgs a, long lon
 #pragma unroll
     for (int c = 0; c < 4; ++c) lr[c] = (e0 + c) < a.split ? a.lr1 : a.lr2;
 #pragma unroll
-    for (int j = 0; j < N; ++j) {
-      f4 s;
-      if (a.init) {
-        s = g[j];
-      } else {
-        s = a.rho * g[j] + a.one_minus_rho * s_old[j];  // numpy: rho*g + (1-rho)*s
-      }
-      st4<false>(a.s[j], i, s);
-      W = W - lr * (a.filtered ? s : g[j]);
-    }
+    for (int j = 0; j < N; ++j)
+      st4<false>(a.s[j], i, mewma_step(W, g[j], s_old[j], a.rho, a.one_minus_rho, lr, a.init, a.filtered));
     st4<false>(a.W, i, W);
   }
 }
 
-template <int... Ns>
-static void launch_mewma_vec(int m, unsigned grid, hipStream_t st, const MewmaArgs& a, long long nvec,
-                             std::integer_sequence<int, Ns...>) {
-  ((m == Ns + 1 ? (void)(mewma_vec_kernel<Ns + 1><<<grid, kBlock, 0, st>>>(a, nvec)) : (void)0), ...);
+static void launch_mewma_vec(int m, unsigned grid, hipStream_t st, const MewmaArgs& a, long long nvec) {
+  dispatch_fanin<1>(m, [&](auto N) { mewma_vec_kernel<decltype(N)::value><<<grid, kBlock, 0, st>>>(a, nvec); });
 }
 
 // Generic case: scalar, arbitrary element stride on the gradient buckets.
@@ -67,17 +56,7 @@ __global__ __launch_bounds__(kBlock) void mewma_scalar_kernel(MewmaArgs a, long 
     const float lr = i < a.split ? a.lr1 : a.lr2;
     for (int j = 0; j < a.n; ++j) {
       const float g = a.g[j][i * a.gstride[j]];
-      float s;
-      if (a.init) {
-        s = g;
-      } else {
-        float t1 = a.rho * g;
-        float t2 = a.one_minus_rho * a.s[j][i];
-        s = t1 + t2;
-      }
-      a.s[j][i] = s;
-      float u = lr * (a.filtered ? s : g);
-      W = W - u;
+      a.s[j][i] = mewma_step(W, g, a.s[j][i], a.rho, a.one_minus_rho, lr, a.init, a.filtered);
     }
     a.W[i] = W;
   }
@@ -93,8 +72,7 @@ extern "C" int cfa_mewma_update_f32(float* W, float* const* s, const float* cons
   if (P == 0 || n == 0) return CFA_OK;
   if (!W || !s || !g) return fail(CFA_E_INVALID, "null W/s/g");
   hipStream_t st = (hipStream_t)stream;
-  for (int done = 0; done < n;) {
-    const int m = (n - done) > CFA_MAX_FANIN ? CFA_MAX_FANIN : (n - done);
+  return for_each_pass(n, [&](int done, int m, bool) -> int {
     MewmaArgs a{};
     a.W = W;
     a.n = m;
@@ -120,8 +98,7 @@ extern "C" int cfa_mewma_update_f32(float* W, float* const* s, const float* cons
       if (nvec > 0) {
         // one workgroup per CU: 0.792 against 0.778 of peak on the same buffers
         // (tools/kernel_rooflines.py --bpc-variants)
-        launch_mewma_vec(m, grid_for_own((nvec + kBlock - 1) / kBlock, 1), st, a, nvec,
-                         std::make_integer_sequence<int, CFA_MAX_FANIN>{});
+        launch_mewma_vec(m, grid_for_own((nvec + kBlock - 1) / kBlock, 1), st, a, nvec);
         if (int rc = check_launch("mewma_vec")) return rc;
       }
       begin = nvec * 4;
@@ -131,8 +108,7 @@ extern "C" int cfa_mewma_update_f32(float* W, float* const* s, const float* cons
                             st>>>(a, begin, (long long)P);
       if (int rc = check_launch("mewma_scalar")) return rc;
     }
-    done += m;
-  }
-  return CFA_OK;
+    return CFA_OK;
+  });
 }
 

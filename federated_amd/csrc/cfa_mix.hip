@@ -11,7 +11,9 @@
 // writes the result once. The work is HBM-bound (0.2-0.45 flop/byte): no MFMA and no LDS
 // staging; coefficients and bucket pointers live in the kernel arguments (SGPRs); every load of
 // a tile is issued before its first use; the fan-in N is a template parameter so the fold is
-// fully unrolled.
+// fully unrolled. The rules' steps (seq_step, div_step, lin_step), the fold, the tile walk and the
+// fan-in dispatch are in cfa_internal.h; the bucket split and the passes of a wide fan-in in
+// cfa_mix_shape.h.
 #include <chrono>
 #include <thread>
 
@@ -136,12 +138,10 @@ namespace {
 // workgroup-per-CU shape of long buckets, see launch_vec_chunk).
 template <int N, int RULE, int U, int POL>
 __global__ __launch_bounds__(kBlock) void mix_vec_kernel(float* out, Fanin f, long long nvec) {
-  constexpr long long kTile = (long long)kBlock * U;
-  const long long full = nvec / kTile;
   // (unused and removed by the compiler when POL == 0)
   const __amdgpu_buffer_rsrc_t w = out_rsrc(out, (unsigned)(nvec * 16));
-  for (long long t = blockIdx.x; t < full; t += gridDim.x) {
-    const long long base = t * kTile + threadIdx.x;
+  const TileWalk<U> tw(nvec);
+  for (const long long base : tw.full_tiles()) {
     f4 v[U][N + 1];
 #pragma unroll
     for (int k = 0; k <= N; ++k)
@@ -156,8 +156,8 @@ __global__ __launch_bounds__(kBlock) void mix_vec_kernel(float* out, Fanin f, lo
         st4<false>(out, base + (long long)u * kBlock, y);
     }
   }
-  if (blockIdx.x == (unsigned)(full % gridDim.x)) {
-    for (long long i = full * kTile + threadIdx.x; i < nvec; i += kBlock) {
+  if (tw.owns_partial()) {
+    for (const long long i : tw.partial_tile()) {
       f4 v[N + 1];
 #pragma unroll
       for (int k = 0; k <= N; ++k) v[k] = ld4<false>(f.src[k], i);
@@ -229,15 +229,11 @@ __global__ __launch_bounds__(kBlock) void mix_scalar_kernel(float* out, ScalarFa
       for (int j = 1; j <= f.n; ++j) w = seq_step(w, f.src[j][i], f.c[j]);
     } else if (rule == CFA_RULE_SEQUENTIAL_DIV) {
       w = w0;
-      for (int j = 1; j <= f.n; ++j) {
-        float t = f.src[j][i] - w;
-        t = f.c[j] * t;
-        t = t / f.d[j];  // between the multiply and the add: not seq_step
-        w = w + t;
-      }
+      bool unused = false;
+      for (int j = 1; j <= f.n; ++j) w = div_step<true>(w, f.src[j][i], f.c[j], f.d[j], 0.0, unused);
     } else {
       w = f.c[0] * w0;
-      for (int j = 1; j <= f.n; ++j) w = fmaf(f.c[j], f.src[j][i], w);
+      for (int j = 1; j <= f.n; ++j) w = lin_step(w, f.src[j][i], f.c[j]);
     }
     if (compress && i >= cp.cbegin && i < cp.cend) w = compress_one(w, w0, cp, kept);
     out[i] = w;
@@ -255,12 +251,10 @@ __global__ __launch_bounds__(kBlock) void compress_kernel(float* y, const float*
   unsigned kept = 0;
   const float thr = (float)cp.thr, rep = (float)cp.rep;
   constexpr int U = 4;  // four float4 of y and ref per lane in flight together
-  constexpr long long kTile = (long long)kBlock * U;
-  const long long full = nvec / kTile;
   f4* y4 = reinterpret_cast<f4*>(y);
   const f4* r4 = reinterpret_cast<const f4*>(ref);
-  for (long long t = blockIdx.x; t < full; t += gridDim.x) {
-    const long long base = t * kTile + threadIdx.x;
+  const TileWalk<U> tw(nvec);
+  for (const long long base : tw.full_tiles()) {
     f4 v[U], r[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -277,8 +271,8 @@ __global__ __launch_bounds__(kBlock) void compress_kernel(float* y, const float*
       y4[base + (long long)u * kBlock] = v[u];  // in place: an sc1 store measured 20% slower, nt 13% slower
     }
   }
-  if (blockIdx.x == (unsigned)(full % gridDim.x)) {
-    for (long long i = full * kTile + threadIdx.x; i < nvec; i += kBlock) {
+  if (tw.owns_partial()) {
+    for (const long long i : tw.partial_tile()) {
       f4 v = y4[i];
       const f4 r = (KIND == 2) ? r4[i] : f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -300,30 +294,8 @@ __global__ __launch_bounds__(kBlock) void compress_kernel(float* y, const float*
 template <int RULE, int U, int POL>
 static void launch_vec_u(int n, unsigned grid, hipStream_t st, float* out, const Fanin& f,
                          long long nvec) {
-#define CFA_CASE(K) \
-  case K:           \
-    mix_vec_kernel<K, RULE, U, POL><<<grid, kBlock, 0, st>>>(out, f, nvec); \
-    break;
-  switch (n) {
-    CFA_CASE(0) CFA_CASE(1) CFA_CASE(2) CFA_CASE(3) CFA_CASE(4) CFA_CASE(5) CFA_CASE(6)
-    CFA_CASE(7) CFA_CASE(8) CFA_CASE(9) CFA_CASE(10) CFA_CASE(11) CFA_CASE(12) CFA_CASE(13)
-    CFA_CASE(14) CFA_CASE(15) CFA_CASE(16)
-    default: break;
-  }
-#undef CFA_CASE
-}
-
-template <int RULE>
-static void launch_vec_chunk(int n, hipStream_t st, float* out, const Fanin& f, long long nvec,
-                             const cfa_launch_t& t);
-
-template <int RULE>
-static void launch_vec(int n, hipStream_t st, float* out, const Fanin& f, long long nvec,
-                       const cfa_launch_t& t) {
-  for_each_chunk(nvec, [&](long long done, long long m) {
-    Fanin g = f;
-    for (int k = 0; k <= n; ++k) g.src[k] = f.src[k] + done * 4;
-    launch_vec_chunk<RULE>(n, st, out + done * 4, g, m, t);
+  dispatch_fanin<0>(n, [&](auto N) {
+    mix_vec_kernel<decltype(N)::value, RULE, U, POL><<<grid, kBlock, 0, st>>>(out, f, nvec);
   });
 }
 
@@ -369,20 +341,22 @@ static void launch_vec_chunk(int n, hipStream_t st, float* out, const Fanin& f, 
   }
 }
 
+template <int RULE>
+static void launch_vec(int n, hipStream_t st, float* out, const Fanin& f, long long nvec,
+                       const cfa_launch_t& t) {
+  for_each_chunk(nvec, [&](long long done, long long m) {
+    Fanin g = f;
+    for (int k = 0; k <= n; ++k) g.src[k] = f.src[k] + done * 4;
+    launch_vec_chunk<RULE>(n, st, out + done * 4, g, m, t);
+  });
+}
+
 template <int KIND>
 static void launch_vec_compress_k(int n, unsigned grid, hipStream_t st, float* out, const Fanin& f,
                                   long long nvec, const CompressParams& cp) {
-#define CFA_CASE(K) \
-  case K:           \
-    mix_vec_compress_kernel<K, KIND><<<grid, kBlock, 0, st>>>(out, f, nvec, cp); \
-    break;
-  switch (n) {
-    CFA_CASE(0) CFA_CASE(1) CFA_CASE(2) CFA_CASE(3) CFA_CASE(4) CFA_CASE(5) CFA_CASE(6)
-    CFA_CASE(7) CFA_CASE(8) CFA_CASE(9) CFA_CASE(10) CFA_CASE(11) CFA_CASE(12) CFA_CASE(13)
-    CFA_CASE(14) CFA_CASE(15) CFA_CASE(16)
-    default: break;
-  }
-#undef CFA_CASE
+  dispatch_fanin<0>(n, [&](auto N) {
+    mix_vec_compress_kernel<decltype(N)::value, KIND><<<grid, kBlock, 0, st>>>(out, f, nvec, cp);
+  });
 }
 
 static void launch_vec_compress(int n, hipStream_t st, float* out, const Fanin& f, long long nvec,
@@ -395,25 +369,14 @@ static void launch_vec_compress(int n, hipStream_t st, float* out, const Fanin& 
   }
 }
 
-// One pass of at most CFA_MAX_FANIN neighbours. Splits the bucket into a scalar head (until
-// every pointer is 16-byte aligned, when they share the same misalignment), a float4 body and
-// a scalar tail. Buckets with different misalignments run entirely on the scalar path.
+// One pass of at most CFA_MAX_FANIN neighbours over the bucket's scalar head, float4 body and
+// scalar tail (BucketSplit); buckets with different misalignments run entirely on the scalar path.
 static int mix_pass(float* out, const float* local, const float* const* nbrs, const float* c,
                     int n, size_t P, int rule, const CompressParams* cp, hipStream_t st,
                     const cfa_launch_t& lc = tune(), const float* div = nullptr) {
-  const uintptr_t mis = addr(out) & 15;
-  bool same = (addr(local) & 15) == mis;
-  for (int j = 0; j < n; ++j) same = same && ((addr(nbrs[j]) & 15) == mis);
-  const bool scalar_only = !same || (mis & 3) != 0;
-  size_t head = 0, nvec = 0;
-  if (!scalar_only) {
-    head = mis ? (16 - mis) / 4 : 0;
-    if (head > P) head = P;
-    nvec = (P - head) / 4;
-  } else {
-    head = P;
-  }
-  const size_t tail_begin = head + nvec * 4;
+  const BucketSplit bs = bucket_split(
+      n + 2, [&](int k) { return k == 0 ? addr(out) : (k == 1 ? addr(local) : addr(nbrs[k - 2])); }, P);
+  const size_t head = bs.head, nvec = bs.nvec;
 
   CompressParams cpv{};
   if (cp) cpv = *cp;
@@ -426,10 +389,7 @@ static int mix_pass(float* out, const float* local, const float* const* nbrs, co
     for (int k = 0; k <= n; ++k) f.d[k] = div ? div[k] : 1.0f;
     set_reciprocals(f, n);
     if (cp) {
-      CompressParams shifted = cpv;
-      shifted.cbegin = cpv.cbegin - (long long)head;
-      shifted.cend = cpv.cend - (long long)head;
-      launch_vec_compress(n, st, out + head, f, (long long)nvec, shifted);
+      launch_vec_compress(n, st, out + head, f, (long long)nvec, shifted(cpv, (long long)head));
     } else if (rule == CFA_RULE_SEQUENTIAL) {
       launch_vec<CFA_RULE_SEQUENTIAL>(n, st, out + head, f, (long long)nvec, lc);
     } else if (rule == CFA_RULE_SEQUENTIAL_DIV) {
@@ -440,7 +400,7 @@ static int mix_pass(float* out, const float* local, const float* const* nbrs, co
     if (int rc = check_launch("mix_vec")) return rc;
   }
   // Scalar pieces: [0, head) and [tail_begin, P).
-  const size_t pieces[2][2] = {{0, head}, {tail_begin, P}};
+  const size_t pieces[2][2] = {{0, head}, {bs.tail_begin, P}};
   for (auto& pc : pieces) {
     const size_t b = pc[0], e = pc[1];
     if (e <= b) continue;
@@ -452,18 +412,15 @@ static int mix_pass(float* out, const float* local, const float* const* nbrs, co
     for (int k = 0; k <= n; ++k) sf.c[k] = c[k];
     for (int k = 0; k <= n; ++k) sf.d[k] = div ? div[k] : 1.0f;
     sf.n = n;
-    CompressParams sc = cpv;
-    sc.cbegin = cpv.cbegin - (long long)b;
-    sc.cend = cpv.cend - (long long)b;
     const long long len = (long long)(e - b);
     mix_scalar_kernel<<<grid_for((len + kBlock - 1) / kBlock), kBlock, 0, st>>>(
-        out + b, sf, len, rule, cp ? 1 : 0, sc);
+        out + b, sf, len, rule, cp ? 1 : 0, shifted(cpv, (long long)b));
     if (int rc = check_launch("mix_scalar")) return rc;
   }
   return CFA_OK;
 }
 
-// Sequential rule over any fan-in: chunks of CFA_MAX_FANIN; chunk k>0 continues from `out`.
+// Sequential rule over any fan-in: passes of CFA_MAX_FANIN (for_each_pass); pass k>0 continues from `out`.
 // The compression epilogue is fused into the (single) pass when n <= CFA_MAX_FANIN; wider
 // fan-ins run it as a separate pass with the untouched pre-mix `local` as DPCM reference.
 static int mix_seq_any(float* out, const float* local, const float* const* nbrs,
@@ -474,19 +431,13 @@ static int mix_seq_any(float* out, const float* local, const float* const* nbrs,
   const bool split_epilogue = cp && n > CFA_MAX_FANIN;
   if (split_epilogue && out == local && needs_ref(cp->mode))
     return fail(CFA_E_INVALID, "in-place DPCM compression needs fan-in <= %d", CFA_MAX_FANIN);
-  int done = 0;
-  const float* w = local;
-  float c[CFA_MAX_FANIN + 1];
-  do {
-    const int m = (n - done) > CFA_MAX_FANIN ? CFA_MAX_FANIN : (n - done);
-    c[0] = 1.0f;
+  const CompressParams* fused = (cp && !split_epilogue) ? cp : nullptr;
+  const int rc = for_each_pass(n, [&](int done, int m, bool) {
+    float c[CFA_MAX_FANIN + 1] = {1.0f};
     for (int j = 0; j < m; ++j) c[j + 1] = alphas[done + j];
-    const CompressParams* fused = (cp && !split_epilogue) ? cp : nullptr;
-    if (int rc = mix_pass(out, w, nbrs + done, c, m, P, CFA_RULE_SEQUENTIAL, fused, st, lc))
-      return rc;
-    done += m;
-    w = out;
-  } while (done < n);
+    return mix_pass(out, done ? out : local, nbrs + done, c, m, P, CFA_RULE_SEQUENTIAL, fused, st, lc);
+  }, true);
+  if (rc) return rc;
   if (split_epilogue)
     return cfa_compress_epilogue_f32(out + cp->cbegin, local + cp->cbegin, cp->mode,
                                      (size_t)(cp->cend - cp->cbegin), cp->kept, st);
@@ -521,24 +472,14 @@ extern "C" int cfa_mix_seq_div_f32(float* out, const float* local, const float* 
   if (int rc = validate_mix(out, local, nbrs, n, P)) return rc;
   if (P == 0) return CFA_OK;
   hipStream_t st = (hipStream_t)stream;
-  int done = 0;
-  const float* w = local;
-  float c[CFA_MAX_FANIN + 1], d[CFA_MAX_FANIN + 1];
-  do {
-    const int m = (n - done) > CFA_MAX_FANIN ? CFA_MAX_FANIN : (n - done);
-    c[0] = 1.0f;
-    d[0] = 1.0f;
+  return for_each_pass(n, [&](int done, int m, bool) {
+    float c[CFA_MAX_FANIN + 1] = {1.0f}, d[CFA_MAX_FANIN + 1] = {1.0f};
     for (int j = 0; j < m; ++j) {
       c[j + 1] = alphas[done + j];
       d[j + 1] = divisors[done + j];
     }
-    if (int rc = mix_pass(out, w, nbrs + done, c, m, P, CFA_RULE_SEQUENTIAL_DIV, nullptr, st,
-                          tune(), d))
-      return rc;
-    done += m;
-    w = out;
-  } while (done < n);
-  return CFA_OK;
+    return mix_pass(out, done ? out : local, nbrs + done, c, m, P, CFA_RULE_SEQUENTIAL_DIV, nullptr, st, tune(), d);
+  }, true);
 }
 
 extern "C" int cfa_mix_f32(float* out, const float* local, const float* const* nbrs,
@@ -547,18 +488,11 @@ extern "C" int cfa_mix_f32(float* out, const float* local, const float* const* n
   if (int rc = validate_mix(out, local, nbrs, n, P)) return rc;
   if (P == 0) return CFA_OK;
   hipStream_t st = (hipStream_t)stream;
-  int done = 0;
-  const float* w = local;
-  float c[CFA_MAX_FANIN + 1];
-  do {
-    const int m = (n - done) > CFA_MAX_FANIN ? CFA_MAX_FANIN : (n - done);
-    c[0] = done == 0 ? coeff[0] : 1.0f;
+  return for_each_pass(n, [&](int done, int m, bool) {
+    float c[CFA_MAX_FANIN + 1] = {done == 0 ? coeff[0] : 1.0f};
     for (int j = 0; j < m; ++j) c[j + 1] = coeff[done + j + 1];
-    if (int rc = mix_pass(out, w, nbrs + done, c, m, P, CFA_RULE_LINEAR, nullptr, st)) return rc;
-    done += m;
-    w = out;
-  } while (done < n);
-  return CFA_OK;
+    return mix_pass(out, done ? out : local, nbrs + done, c, m, P, CFA_RULE_LINEAR, nullptr, st);
+  }, true);
 }
 
 extern "C" int cfa_mix_seq_compress_f32(float* out, const float* local, const float* const* nbrs,

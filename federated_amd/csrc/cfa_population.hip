@@ -1,7 +1,9 @@
 // cfa_population.hip — whole-population rounds: the CSR one-launch kernel
 // (cfa_mix_population_f32) and the sliding-window passes (cfa_mix_window_f32) that load each
 // row of a ring window once for up to 8 consecutive devices, and the sliding ring round
-// (cfa_mix_ring_slide_f32) that reads every row of a run of ring devices once.
+// (cfa_mix_ring_slide_f32) that reads every row of a run of ring devices once, and the CFA-GE
+// population step. Every rule's step (seq_step, lin_step, tf1_first / tf1_step, mewma_step,
+// split_sum) is the one definition of cfa_internal.h.
 #include <type_traits>
 
 #include "cfa_internal.h"
@@ -57,14 +59,8 @@ __global__ __launch_bounds__(kBlock) void population_kernel(float* const* out_pt
       for (int u = 0; u < U; ++u) x[u] = ok[u] ? ld4<true>(s, idx[u]) : f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        if constexpr (RULE == CFA_RULE_SEQUENTIAL) {
-          w[u] = seq_step(w[u], x[u], c);
-        } else {
-          w[u].x = fmaf(c, x[u].x, w[u].x);
-          w[u].y = fmaf(c, x[u].y, w[u].y);
-          w[u].z = fmaf(c, x[u].z, w[u].z);
-          w[u].w = fmaf(c, x[u].w, w[u].w);
-        }
+        if constexpr (RULE == CFA_RULE_SEQUENTIAL) w[u] = seq_step(w[u], x[u], c);
+        else w[u] = lin_step(w[u], x[u], c);
       }
     }
 #pragma unroll
@@ -80,11 +76,8 @@ __global__ __launch_bounds__(kBlock) void population_kernel(float* const* out_pt
     for (int e = e0 + 1; e < e1; ++e) {
       const float x = src_ptrs[csr_idx[e]][i];
       const float c = csr_coef[e];
-      if constexpr (RULE == CFA_RULE_SEQUENTIAL) {
-        w = seq_step(w, x, c);
-      } else {
-        w = fmaf(c, x, w);
-      }
+      if constexpr (RULE == CFA_RULE_SEQUENTIAL) w = seq_step(w, x, c);
+      else w = lin_step(w, x, c);
     }
     out[i] = w;
   }
@@ -128,15 +121,12 @@ __global__ __launch_bounds__(kBlock) void population_tf1_kernel(float* const* ou
       const f4 x1 = ld4<true>(src_ptrs[csr_idx[e0 + 1]], i);
       double w[4];
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float dd = x1[c] - lv[c];                      // fp32 - fp32
-        w[c] = (double)lv[c] + csr_coef[e0 + 1] * (double)dd;  // fp64 from here on
-      }
+      for (int c = 0; c < 4; ++c) w[c] = tf1_first(lv[c], x1[c], csr_coef[e0 + 1]);  // fp64 from here on
       for (int e = e0 + 2; e < e1; ++e) {
         const f4 x = ld4<true>(src_ptrs[csr_idx[e]], i);
         const double a = csr_coef[e];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) w[c] = w[c] + a * ((double)x[c] - w[c]);
+        for (int c = 0; c < 4; ++c) w[c] = tf1_step(w[c], x[c], a);
       }
 #pragma unroll
       for (int c = 0; c < 4; ++c) y[c] = epi(w[c], lv[c], 4 * i + c);
@@ -150,9 +140,8 @@ __global__ __launch_bounds__(kBlock) void population_tf1_kernel(float* const* ou
       if (e1 - e0 <= 1) {
         y = epi0(lv, i);
       } else {
-        const float dd = src_ptrs[csr_idx[e0 + 1]][i] - lv;
-        double w = (double)lv + csr_coef[e0 + 1] * (double)dd;
-        for (int e = e0 + 2; e < e1; ++e) w = w + csr_coef[e] * ((double)src_ptrs[csr_idx[e]][i] - w);
+        double w = tf1_first(lv, src_ptrs[csr_idx[e0 + 1]][i], csr_coef[e0 + 1]);
+        for (int e = e0 + 2; e < e1; ++e) w = tf1_step(w, src_ptrs[csr_idx[e]][i], csr_coef[e]);
         y = epi(w, lv, i);
       }
       out[i] = y;
@@ -655,11 +644,8 @@ __global__ __launch_bounds__(kBlock) void ge_step_kernel(GeStepArgs a, long long
   if (d >= (int)gridDim.y - a.rM) {  // reduction rows: the split sum in split order (deterministic)
     const long long m = d - ((int)gridDim.y - a.rM);
     const float* w = a.rws + m * a.rsp * P;
-    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < P; i += (long long)gridDim.x * kBlock) {
-      float s = w[i];
-      for (int sp = 1; sp < a.rsp; ++sp) s += w[(long long)sp * P + i];
-      a.rout[m * P + i] = s;
-    }
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < P; i += (long long)gridDim.x * kBlock)
+      a.rout[m * P + i] = split_sum(w + i, a.rsp, P);
     return;
   }
   const int e0 = a.ptr[d], e1 = a.ptr[d + 1];
@@ -677,9 +663,7 @@ __global__ __launch_bounds__(kBlock) void ge_step_kernel(GeStepArgs a, long long
       const float* gp = a.grad[e];
       const f4 g = gp ? ld4<false>(gp, i) : f4{0.f, 0.f, 0.f, 0.f};
       const f4 s_old = ld4<false>(a.state[e], i);
-      const f4 s = a.rho * g + a.one_minus_rho * s_old;
-      st4<false>(a.state[e], i, s);
-      w = w - lr * (a.filtered ? s : g);
+      st4<false>(a.state[e], i, mewma_step(w, g, s_old, a.rho, a.one_minus_rho, lr, false, a.filtered));
     }
     st4<false>(out, i, w);
   }
@@ -690,11 +674,7 @@ __global__ __launch_bounds__(kBlock) void ge_step_kernel(GeStepArgs a, long long
       const float lr = ge_lr(a, i);
       for (int e = e0 + 1; e < e1; ++e) {
         const float g = a.grad[e] ? a.grad[e][i] : 0.f;
-        const float t1 = a.rho * g;
-        const float t2 = a.one_minus_rho * a.state[e][i];
-        const float s = t1 + t2;
-        a.state[e][i] = s;
-        w = w - lr * (a.filtered ? s : g);
+        a.state[e][i] = mewma_step(w, g, a.state[e][i], a.rho, a.one_minus_rho, lr, false, a.filtered);
       }
       out[i] = w;
     }

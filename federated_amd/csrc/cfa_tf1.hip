@@ -4,8 +4,9 @@
 // 225-273, cfa_ge_2stage.py:76-83, 331-371, 593-621; the fp64 server-side folds of
 // FL_over_MQTT/PS_server.py:130-133, learner_consensus.py:151-152,
 // federated_sample_CNN_CFA_FA.py:86-89, 130-133, 280-283.
-#include <utility>
-
+// The chain's steps (tf1_first, tf1_step), the fp64 divisor step (div_step_f64) and the fp64 MEWMA
+// step (mewma_step_f64) are in cfa_internal.h, with the tile walk and the fan-in dispatch; the
+// bucket split and the passes of a wide fan-in in cfa_mix_shape.h.
 #include "cfa_internal.h"
 
 namespace {
@@ -55,15 +56,12 @@ __device__ __forceinline__ void tf1_vec(void* out, const Sc1Out& o, const Tf1Fan
     for (int c = 0; c < W; ++c) w[c] = w64[c];
   } else {
 #pragma unroll
-    for (int c = 0; c < W; ++c) {
-      const float d = x[0][c] - l[c];            // fp32 - fp32 (both operands fp32)
-      w[c] = (double)l[c] + f.a[0] * (double)d;  // np.float64 * fp32 -> fp64; fp32 + fp64 -> fp64
-    }
+    for (int c = 0; c < W; ++c) w[c] = tf1_first(l[c], x[0][c], f.a[0]);
   }
 #pragma unroll
   for (int j = j0; j < N; ++j)
 #pragma unroll
-    for (int c = 0; c < W; ++c) w[c] = w[c] + f.a[j] * ((double)x[j][c] - w[c]);
+    for (int c = 0; c < W; ++c) w[c] = tf1_step(w[c], x[j][c], f.a[j]);
   if (OUT != kOutScratch64 && compress) {
     const long long e0 = i * W;
 #pragma unroll
@@ -89,13 +87,11 @@ __global__ __launch_bounds__(kBlock) void mix_tf1_vec_kernel(void* out, Tf1Fanin
                                                               CompressParams cp, int compress) {
   using V = typename Tf1Vec<OUT>::type;
   constexpr int W = Tf1Vec<OUT>::W;
-  constexpr long long kTile = (long long)kBlock * U;
   unsigned kept = 0;
   const Sc1Out o = sc1_out(out, nvec * 16);  // used by the fp32 output only (16-B vectors)
-  const long long full = nvec / kTile;
   auto ld = [](const float* p, long long i) { return __builtin_nontemporal_load(reinterpret_cast<const V*>(p) + i); };
-  for (long long t = blockIdx.x; t < full; t += gridDim.x) {
-    const long long base = t * kTile + threadIdx.x;
+  const TileWalk<U> tw(nvec);
+  for (const long long base : tw.full_tiles()) {
     V x[U][N], l[U];
 #pragma unroll
     for (int k = 0; k < N; ++k)
@@ -114,8 +110,8 @@ __global__ __launch_bounds__(kBlock) void mix_tf1_vec_kernel(void* out, Tf1Fanin
     for (int u = 0; u < U; ++u)
       tf1_vec<N, FROM64, OUT>(out, o, f, x[u], l[u], w64[u], base + (long long)u * kBlock, cp, compress, kept);
   }
-  if (blockIdx.x == (unsigned)(full % gridDim.x)) {
-    for (long long i = full * kTile + threadIdx.x; i < nvec; i += kBlock) {
+  if (tw.owns_partial()) {
+    for (const long long i : tw.partial_tile()) {
       V x[N];
 #pragma unroll
       for (int k = 0; k < N; ++k) x[k] = ld(f.src[k], i);
@@ -144,11 +140,10 @@ __global__ __launch_bounds__(kBlock) void mix_tf1_scalar_kernel(void* out, int o
     if (f.w64) {
       w = f.w64[i];
     } else {
-      const float d = f.src[0][i] - l;
-      w = (double)l + f.a[0] * (double)d;
+      w = tf1_first(l, f.src[0][i], f.a[0]);
       j = 1;
     }
-    for (; j < n; ++j) w = w + f.a[j] * ((double)f.src[j][i] - w);
+    for (; j < n; ++j) w = tf1_step(w, f.src[j][i], f.a[j]);
     if (out_mode != kOutScratch64 && compress && i >= cp.cbegin && i < cp.cend)
       w = compress_one_d(w, l, cp, kept);
     if (out_mode == kOutF32)
@@ -170,20 +165,6 @@ struct F64Fanin {
   int fast_div;                          // every d[j] in [2^-20, 2^20]
 };
 
-// Correctly rounded fp64 a / b (Markstein): q = RN(a * rb) with rb = RN(1/b) is within 1 ulp,
-// the remainder a - b q is exact (one fma), and RN(q + r * rb) is the correctly rounded quotient
-// when nothing under- or overflows; |a| in [2^-900, 2^900] and b in [2^-20, 2^20] guarantee
-// that, everything else takes the IEEE division. (The fp32 fold's one-multiply form, div_rd in
-// cfa_internal.h, needs a format twice as wide; fp64 has none on the GPU.)
-__device__ __forceinline__ double ddiv_rn(double a, double b, double rb, bool fast) {
-  const double aa = __builtin_fabs(a);
-  if (fast && aa >= 0x1p-900 && aa <= 0x1p900) {
-    const double q = a * rb;
-    const double r = __builtin_fma(-q, b, a);
-    return __builtin_fma(r, rb, q);
-  }
-  return a / b;
-}
 // rule: CFA_RULE_SEQUENTIAL  w = w + a*(x - w)
 //       CFA_RULE_SEQUENTIAL_DIV  w = w + (a*(x - w))/d
 //       CFA_RULE_ACCUMULATE  w = w + a*x
@@ -197,14 +178,13 @@ __global__ __launch_bounds__(kBlock) void mix_tf1_f64_kernel(double* out, F64Fan
     double w = f.src[0][i];
     int j = 1;
     if (step0_f32 && f.m >= 1) {  // both operands fp32 arrays in the reference: fp32 subtraction
-      const float d = (float)f.src[1][i] - (float)w;
-      w = w + f.a[1] * (double)d;
+      w = tf1_first(w, (float)f.src[1][i], f.a[1]);
       j = 2;
     }
     if (rule == CFA_RULE_SEQUENTIAL) {
-      for (; j <= f.m; ++j) w = w + f.a[j] * (f.src[j][i] - w);
+      for (; j <= f.m; ++j) w = tf1_step(w, f.src[j][i], f.a[j]);
     } else if (rule == CFA_RULE_SEQUENTIAL_DIV) {
-      for (; j <= f.m; ++j) w = w + (f.a[j] * (f.src[j][i] - w)) / f.d[j];
+      for (; j <= f.m; ++j) w = div_step_f64<true>(w, f.src[j][i], f.a[j], f.d[j], 0.0, false);
     } else {
       for (; j <= f.m; ++j) w = w + f.a[j] * f.src[j][i];
     }
@@ -231,16 +211,15 @@ __device__ __forceinline__ d2 fold_d2(const d2 (&v)[N + 1], const F64Fanin& f, l
     double w = v[0][c];
     int j = 1;
     if constexpr (STEP0F32) {  // both operands fp32 arrays in the reference: fp32 subtraction
-      const float d = (float)v[1][c] - (float)w;
-      w = w + f.a[1] * (double)d;
+      w = tf1_first(w, (float)v[1][c], f.a[1]);
       j = 2;
     }
 #pragma unroll
     for (int k = 1; k <= N; ++k) {
       if (k < j) continue;
-      if constexpr (RULE == CFA_RULE_SEQUENTIAL) w = w + f.a[k] * (v[k][c] - w);
+      if constexpr (RULE == CFA_RULE_SEQUENTIAL) w = tf1_step(w, v[k][c], f.a[k]);
       else if constexpr (RULE == CFA_RULE_SEQUENTIAL_DIV)
-        w = w + ddiv_rn(f.a[k] * (v[k][c] - w), f.d[k], f.r[k], f.fast_div);
+        w = div_step_f64<false>(w, v[k][c], f.a[k], f.d[k], f.r[k], f.fast_div);
       else w = w + f.a[k] * v[k][c];
     }
     if (compress) {
@@ -257,12 +236,10 @@ __global__ __launch_bounds__(kBlock) void fold_f64_vec_kernel(double* out, F64Fa
                                                                const double* ref, CompressParams cp,
                                                                int compress) {
   constexpr int U = 2;
-  constexpr long long kTile = (long long)kBlock * U;
-  const long long full = nvec2 / kTile;
   const Sc1Out o = sc1_out(out, nvec2 * 16);
   unsigned kept = 0;
-  for (long long t = blockIdx.x; t < full; t += gridDim.x) {
-    const long long base = t * kTile + threadIdx.x;
+  const TileWalk<U> tw(nvec2);
+  for (const long long base : tw.full_tiles()) {
     d2 v[U][N + 1];
 #pragma unroll
     for (int k = 0; k <= N; ++k)
@@ -275,8 +252,8 @@ __global__ __launch_bounds__(kBlock) void fold_f64_vec_kernel(double* out, F64Fa
       st16_sc1(o, i, fold_d2<N, RULE, STEP0F32>(v[u], f, i, ref, cp, compress, kept));
     }
   }
-  if (blockIdx.x == (unsigned)(full % gridDim.x)) {
-    for (long long i = full * kTile + threadIdx.x; i < nvec2; i += kBlock) {
+  if (tw.owns_partial()) {
+    for (const long long i : tw.partial_tile()) {
       d2 v[N + 1];
 #pragma unroll
       for (int k = 0; k <= N; ++k) v[k] = reinterpret_cast<const d2*>(f.src[k])[i];
@@ -289,17 +266,9 @@ __global__ __launch_bounds__(kBlock) void fold_f64_vec_kernel(double* out, F64Fa
 template <int RULE, bool STEP0F32>
 static void launch_fold_vec(int m, unsigned grid, hipStream_t st, double* out, const F64Fanin& f,
                             long long nvec2, const double* ref, const CompressParams& cp, int compress) {
-#define CFA_CASE(K) \
-  case K:           \
-    fold_f64_vec_kernel<K, RULE, STEP0F32><<<grid, kBlock, 0, st>>>(out, f, nvec2, ref, cp, compress); \
-    break;
-  switch (m) {
-    CFA_CASE(1) CFA_CASE(2) CFA_CASE(3) CFA_CASE(4) CFA_CASE(5) CFA_CASE(6) CFA_CASE(7)
-    CFA_CASE(8) CFA_CASE(9) CFA_CASE(10) CFA_CASE(11) CFA_CASE(12) CFA_CASE(13) CFA_CASE(14)
-    CFA_CASE(15) CFA_CASE(16)
-    default: break;
-  }
-#undef CFA_CASE
+  dispatch_fanin<1>(m, [&](auto N) {
+    fold_f64_vec_kernel<decltype(N)::value, RULE, STEP0F32><<<grid, kBlock, 0, st>>>(out, f, nvec2, ref, cp, compress);
+  });
 }
 
 struct MewmaF64Args {
@@ -312,15 +281,7 @@ struct MewmaF64Args {
   long long split;
   int init, filtered, mask;  // mask: CFA_TF1_STATE_F32 | CFA_TF1_GRAD_F32 | CFA_TF1_W_F32
 };
-// Python-float scalar times an array, in the array's dtype (numpy 2: the scalar is weak).
-__device__ __forceinline__ double scale(double c, double x, bool f32) {
-  return f32 ? (double)((float)c * (float)x) : c * x;
-}
-// cfa_ge_2stage.py:331-371 / :593-621 with numpy 2 promotion per operation:
-//   s_j = rho*g_j + (1-rho)*s_j (or g_j at init), stored in the state array's dtype;
-//   W   = W - lr*(filtered ? s_j : g_j).
-// Each product is computed in its array's dtype; a sum or difference is fp32 only when both
-// operands are fp32, and W stays fp32 only while every update it receives is fp32.
+// cfa_ge_2stage.py:331-371 / :593-621 with numpy 2 promotion per operation (mewma_step_f64).
 __global__ __launch_bounds__(kBlock) void mewma_tf1_f64_kernel(MewmaF64Args a, long long P) {
   const bool s32 = a.mask & CFA_TF1_STATE_F32, g32 = a.mask & CFA_TF1_GRAD_F32;
   for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < P;
@@ -330,24 +291,7 @@ __global__ __launch_bounds__(kBlock) void mewma_tf1_f64_kernel(MewmaF64Args a, l
     const double lr = i < a.split ? a.lr1 : a.lr2;
     for (int j = 0; j < a.n; ++j) {
       const double g = a.g[j][i * a.gstride[j]];
-      double s;
-      if (a.init) {
-        s = g;
-      } else {
-        const double t1 = scale(a.rho, g, g32);
-        const double t2 = scale(a.one_minus_rho, a.s[j][i], s32);
-        s = (g32 && s32) ? (double)((float)t1 + (float)t2) : t1 + t2;
-      }
-      if (s32) s = (double)(float)s;
-      a.s[j][i] = s;
-      const bool u32 = a.filtered ? s32 : g32;
-      const double t = scale(lr, a.filtered ? s : g, u32);
-      if (w32 && u32) {
-        W = (double)((float)W - (float)t);
-      } else {
-        W = W - t;
-        w32 = false;
-      }
+      a.s[j][i] = mewma_step_f64(W, w32, g, a.s[j][i], a.rho, a.one_minus_rho, lr, a.init, a.filtered, s32, g32);
     }
     a.W[i] = W;
   }
@@ -377,24 +321,8 @@ __global__ __launch_bounds__(kBlock) void mewma_tf1_f64_vec_kernel(MewmaF64Args 
       const double lr = 2 * i + c < a.split ? a.lr1 : a.lr2;
 #pragma unroll
       for (int j = 0; j < N; ++j) {
-        double sv;
-        if (a.init) {
-          sv = g[j][c];
-        } else {
-          const double t1 = scale(a.rho, g[j][c], g32);
-          const double t2 = scale(a.one_minus_rho, so[j][c], s32);
-          sv = (g32 && s32) ? (double)((float)t1 + (float)t2) : t1 + t2;
-        }
-        if (s32) sv = (double)(float)sv;
-        sn[j][c] = sv;
-        const bool u32 = a.filtered ? s32 : g32;
-        const double t = scale(lr, a.filtered ? sv : g[j][c], u32);
-        if (w32 && u32) {
-          W = (double)((float)W - (float)t);
-        } else {
-          W = W - t;
-          w32 = false;
-        }
+        const double so_jc = a.init ? 0.0 : so[j][c];  // not loaded at init
+        sn[j][c] = mewma_step_f64(W, w32, g[j][c], so_jc, a.rho, a.one_minus_rho, lr, a.init, a.filtered, s32, g32);
       }
       Wv[c] = W;
     }
@@ -406,30 +334,19 @@ __global__ __launch_bounds__(kBlock) void mewma_tf1_f64_vec_kernel(MewmaF64Args 
   }
 }
 
-template <int... Ns>
-static void launch_mewma_f64_vec(int m, unsigned grid, hipStream_t st, const MewmaF64Args& a, long long nvec2,
-                                 std::integer_sequence<int, Ns...>) {
-  if (a.mask)
-    ((m == Ns + 1 ? (void)(mewma_tf1_f64_vec_kernel<Ns + 1, true><<<grid, kBlock, 0, st>>>(a, nvec2)) : (void)0), ...);
-  else
-    ((m == Ns + 1 ? (void)(mewma_tf1_f64_vec_kernel<Ns + 1, false><<<grid, kBlock, 0, st>>>(a, nvec2)) : (void)0),
-     ...);
+static void launch_mewma_f64_vec(int m, unsigned grid, hipStream_t st, const MewmaF64Args& a, long long nvec2) {
+  dispatch_fanin<1>(m, [&](auto N) {
+    if (a.mask) mewma_tf1_f64_vec_kernel<decltype(N)::value, true><<<grid, kBlock, 0, st>>>(a, nvec2);
+    else mewma_tf1_f64_vec_kernel<decltype(N)::value, false><<<grid, kBlock, 0, st>>>(a, nvec2);
+  });
 }
 
 template <bool FROM64, int OUT, int U>
 static void launch_tf1_vec_u(int n, unsigned grid, hipStream_t st, void* out, const Tf1Fanin& f,
                              long long nvec, const CompressParams& cp, int compress) {
-#define CFA_CASE(K) \
-  case K:           \
-    mix_tf1_vec_kernel<K, FROM64, OUT, U><<<grid, kBlock, 0, st>>>(out, f, nvec, cp, compress); \
-    break;
-  switch (n) {
-    CFA_CASE(1) CFA_CASE(2) CFA_CASE(3) CFA_CASE(4) CFA_CASE(5) CFA_CASE(6) CFA_CASE(7)
-    CFA_CASE(8) CFA_CASE(9) CFA_CASE(10) CFA_CASE(11) CFA_CASE(12) CFA_CASE(13) CFA_CASE(14)
-    CFA_CASE(15) CFA_CASE(16)
-    default: break;
-  }
-#undef CFA_CASE
+  dispatch_fanin<1>(n, [&](auto N) {
+    mix_tf1_vec_kernel<decltype(N)::value, FROM64, OUT, U><<<grid, kBlock, 0, st>>>(out, f, nvec, cp, compress);
+  });
 }
 
 // Launch shape of the TF1 vector kernel: the library default or an explicit CFA_VEC_PER_LANE /
@@ -457,8 +374,9 @@ static void launch_tf1_vec(int n, hipStream_t st, void* out, const Tf1Fanin& f, 
 // body of nvec vectors, a scalar tail. out_mode: kOutF32 (last pass, fp32 out), kOutScratch64
 // (fp64 scratch of a chained pass) or kOutF64 (last pass, unrounded fp64 out).
 static int tf1_pass(void* out, int out_mode, const float* local, const double* w64,
-                    const float* const* nbrs, const double* a, int m, size_t P, size_t head,
-                    size_t nvec, const CompressParams& cp, int compress, hipStream_t st) {
+                    const float* const* nbrs, const double* a, int m, size_t P, const BucketSplit& bs,
+                    const CompressParams& cp, int compress, hipStream_t st) {
+  const size_t head = bs.head, nvec = bs.nvec;
   auto fanin_at = [&](size_t b) {
     Tf1Fanin f{};
     f.local = local + b;
@@ -472,17 +390,11 @@ static int tf1_pass(void* out, int out_mode, const float* local, const double* w
   auto out_at = [&](size_t b) -> void* {
     return out_mode != kOutF32 ? (void*)((double*)out + b) : (void*)((float*)out + b);
   };
-  auto shifted = [&](size_t b) {
-    CompressParams c = cp;
-    c.cbegin = cp.cbegin - (long long)b;
-    c.cend = cp.cend - (long long)b;
-    return c;
-  };
   if (nvec > 0) {
     const Tf1Fanin f = fanin_at(head);
     // the fp64-output (wide) form runs one workgroup per CU: 0.749 against 0.729 of peak on the
     // same buffers (tools/kernel_rooflines.py --bpc-variants 2,1); the fp32 outputs keep two
-    const CompressParams c = shifted(head);
+    const CompressParams c = shifted(cp, (long long)head);
     void* o = out_at(head);
     const long long nv = (long long)nvec;
     if (out_mode == kOutF32) {
@@ -497,14 +409,13 @@ static int tf1_pass(void* out, int out_mode, const float* local, const double* w
     }
     if (int rc = check_launch("mix_tf1_vec")) return rc;
   }
-  const size_t tail_begin = head + nvec * 4;
-  const size_t pieces[2][2] = {{0, head}, {tail_begin, P}};
+  const size_t pieces[2][2] = {{0, head}, {bs.tail_begin, P}};
   for (auto& pc : pieces) {
     const size_t b = pc[0], e = pc[1];
     if (e <= b) continue;
     const long long len = (long long)(e - b);
     mix_tf1_scalar_kernel<<<grid_for((len + kBlock - 1) / kBlock), kBlock, 0, st>>>(
-        out_at(b), out_mode, fanin_at(b), m, len, shifted(b), compress);
+        out_at(b), out_mode, fanin_at(b), m, len, shifted(cp, (long long)b), compress);
     if (int rc = check_launch("mix_tf1_scalar")) return rc;
   }
   return CFA_OK;
@@ -557,15 +468,9 @@ int mix_tf1_impl(void* out, bool out64, const float* local, const float* const* 
   if (P == 0) return CFA_OK;
   // Body/head/tail split shared by every pass (the fp32 pointers decide it; fp64 buckets, the
   // scratch and an fp64 out, are indexed like the bucket and only need 8-byte alignment).
-  const uintptr_t mis = addr(out64 ? (const void*)local : out) & 15;
-  bool same = (addr(local) & 15) == mis;
-  for (int j = 0; j < n; ++j) same = same && ((addr(nbrs[j]) & 15) == mis);
-  size_t head = P, nvec = 0;
-  if (same && (mis & 3) == 0) {
-    head = mis ? (16 - mis) / 4 : 0;
-    if (head > P) head = P;
-    nvec = (P - head) / 4;
-  }
+  BucketSplit bs = bucket_split(n + 2, [&](int k) {
+    return k == 0 ? addr(out64 ? (const void*)local : out) : (k == 1 ? addr(local) : addr(nbrs[k - 2]));
+  }, P);
   // chained passes carry w in fp64: in an fp64 out itself, else in the scratch bucket
   double* scratch = out64 ? static_cast<double*>(out) : scratch_in;
   bool owned = false;
@@ -582,20 +487,13 @@ int mix_tf1_impl(void* out, bool out64, const float* local, const float* const* 
   // The vector kernel stores an fp64 output (the fp64 out, or the scratch of chained passes) as
   // 16-B vectors, so that output's body must start 16-B aligned; such buckets only promise 8 B
   // (an fp64 view at an odd element), and then the scalar kernel takes the whole bucket.
-  auto body16 = [&](const void* p) { return ((addr(p) + 8 * head) & 15) == 0; };
-  if (nvec && ((out64 && !body16(out)) || (n > CFA_MAX_FANIN && !body16(scratch)))) {
-    head = P;
-    nvec = 0;
-  }
-  int rc = CFA_OK;
-  for (int done = 0; done < n && rc == CFA_OK;) {
-    const int m = (n - done) > CFA_MAX_FANIN ? CFA_MAX_FANIN : (n - done);
-    const bool last = done + m == n;
+  auto body16 = [&](const void* p) { return ((addr(p) + 8 * bs.head) & 15) == 0; };
+  if (bs.nvec && ((out64 && !body16(out)) || (n > CFA_MAX_FANIN && !body16(scratch)))) bs = all_scalar(P);
+  const int rc = for_each_pass(n, [&](int done, int m, bool last) {
     const int out_mode = !last ? kOutScratch64 : (out64 ? kOutF64 : kOutF32);
-    rc = tf1_pass(last ? out : (void*)scratch, out_mode, local, done ? scratch : nullptr, nbrs + done,
-                  alphas + done, m, P, head, nvec, cp, last ? compress : 0, st);
-    done += m;
-  }
+    return tf1_pass(last ? out : (void*)scratch, out_mode, local, done ? scratch : nullptr, nbrs + done,
+                    alphas + done, m, P, bs, cp, last ? compress : 0, st);
+  });
   if (owned) {
     hipError_t e = hipFreeAsync(scratch, st);
     if (rc == CFA_OK && e != hipSuccess) return fail(CFA_E_HIP, "hipFreeAsync: %s", hipGetErrorString(e));
@@ -648,11 +546,9 @@ int fold_f64(double* out, const double* local, const double* const* nbrs, const 
   cp.cend = (long long)cend;
   cp.kept = kept_count;
   const unsigned grid = grid_for(((long long)P + kBlock - 1) / kBlock);
-  int done = 0;
-  const double* w = local;
-  do {  // n == 0 runs one pass that copies local (and applies the epilogue)
-    const int m = (n - done) > CFA_MAX_FANIN ? CFA_MAX_FANIN : (n - done);
-    const bool last = done + m == n;
+  // n == 0 runs one pass that copies local (and applies the epilogue)
+  return for_each_pass(n, [&](int done, int m, bool last) -> int {
+    const double* w = done ? out : local;
     F64Fanin f{};
     f.src[0] = w;
     f.m = m;
@@ -687,17 +583,12 @@ int fold_f64(double* out, const double* local, const double* const* nbrs, const 
     if (b < (long long)P) {
       F64Fanin ft = f;
       for (int j = 0; j <= m; ++j) ft.src[j] = f.src[j] + b;
-      CompressParams ct = cp;
-      ct.cbegin = cp.cbegin - b;
-      ct.cend = cp.cend - b;
-      mix_tf1_f64_kernel<<<b ? 1u : grid, kBlock, 0, st>>>(out + b, ft, (long long)P - b, rule, s0, local + b, ct,
-                                                          cmp);
+      mix_tf1_f64_kernel<<<b ? 1u : grid, kBlock, 0, st>>>(out + b, ft, (long long)P - b, rule, s0, local + b,
+                                                          shifted(cp, b), cmp);
       if (int rc = check_launch("fold_f64")) return rc;
     }
-    done += m;
-    w = out;
-  } while (done < n);
-  return CFA_OK;
+    return CFA_OK;
+  }, true);
 }
 }  // namespace
 
@@ -727,8 +618,7 @@ extern "C" int cfa_mewma_tf1_f64(double* W, double* const* s, const double* cons
   if (P == 0 || n == 0) return CFA_OK;
   if (!W) return fail(CFA_E_INVALID, "null W");
   hipStream_t st = (hipStream_t)stream;
-  for (int done = 0; done < n;) {
-    const int m = (n - done) > CFA_MAX_FANIN ? CFA_MAX_FANIN : (n - done);
+  return for_each_pass(n, [&](int done, int m, bool) -> int {
     MewmaF64Args a{};
     a.W = W;
     a.n = m;
@@ -754,8 +644,7 @@ extern "C" int cfa_mewma_tf1_f64(double* W, double* const* s, const double* cons
     const long long nvec2 = vec ? (long long)P / 2 : 0;
     if (nvec2 > 0) {
       // one workgroup per CU: 0.733 against 0.714 of peak on the same buffers (--bpc-variants 2,1)
-      launch_mewma_f64_vec(m, grid_for_own((nvec2 + kBlock - 1) / kBlock, 1), st, a, nvec2,
-                           std::make_integer_sequence<int, CFA_MAX_FANIN>{});
+      launch_mewma_f64_vec(m, grid_for_own((nvec2 + kBlock - 1) / kBlock, 1), st, a, nvec2);
       if (int rc = check_launch("mewma_tf1_f64_vec")) return rc;
     }
     if (2 * nvec2 < (long long)P) {  // unaligned / strided buckets, or the odd last element
@@ -771,8 +660,7 @@ extern "C" int cfa_mewma_tf1_f64(double* W, double* const* s, const double* cons
           t, (long long)P - b);
       if (int rc = check_launch("mewma_tf1_f64")) return rc;
     }
-    done += m;
-  }
-  return CFA_OK;
+    return CFA_OK;
+  });
 }
 
