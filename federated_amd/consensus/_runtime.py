@@ -9,8 +9,9 @@
   libcfa kernel that folds all n neighbours (plus the optional fused compression epilogue).
   By default the kernel reads the pinned rows and writes the pinned result in place over PCIe
   (zero-copy: ``SINGLE_ZERO_COPY`` for fp32, ``TF1_ZERO_COPY`` for the fp64 TF1 buckets);
-  switched off, the buckets move by one H2D and one D2H copy instead. Large mixes take a
-  chunk pipeline. There is no CPU fallback: without a GPU the engine raises.
+  switched off, the same rows move by one H2D and one D2H copy instead. Either way an operation
+  has one body, written against a ``_RowPlan``; only the plan knows where the rows live. Large
+  mixes take a chunk pipeline. There is no CPU fallback: without a GPU the engine raises.
 """
 from __future__ import annotations
 
@@ -104,6 +105,50 @@ def _layout_of(arrays) -> BucketLayout:
     return lay
 
 
+def _compress_range(layout: BucketLayout, compress: Optional[Tuple[int, int]]) -> Tuple[int, int, int]:
+    """``compress=(mode, layer)`` as (mode, begin, end): that layer's elements in the bucket;
+    (0, 0, 0) without compression."""
+    if compress is None:
+        return 0, 0, 0
+    mode, layer = compress
+    b, e = layout.segment(layer)
+    if not (0 <= b <= e <= layout.P):
+        raise ValueError("bad compression layer")
+    return int(mode), b, e
+
+
+def _lr_split(layout: BucketLayout, lrs: Sequence[float]) -> Tuple[float, float, int]:
+    """Per-layer learning rates as (lr1, lr2, split): lr1 below element ``split``, lr2 from it.
+    Layers with the first rate must precede the others (layer 1 then layer 2)."""
+    first_other = next((k for k in range(len(lrs)) if lrs[k] != lrs[0]), len(lrs))
+    if any(lr != lrs[-1] for lr in lrs[first_other:]):
+        raise ValueError("learning rates must be one value for the leading layers, one for the rest")
+    return float(lrs[0]), float(lrs[-1]), int(layout.offsets[first_other])
+
+
+def _runs(flags) -> list:
+    """Maximal runs of consecutive tensors sharing a flag: [(first, last + 1, flag)]."""
+    runs, k = [], 0
+    while k < len(flags):
+        e = k
+        while e < len(flags) and flags[e] == flags[k]:
+            e += 1
+        runs.append((k, e, flags[k]))
+        k = e
+    return runs
+
+
+def _run_bounds(layout: BucketLayout, flags) -> list:
+    """``_runs(flags)`` in elements of the bucket: [(begin, end, flag)], one launch each."""
+    return [(int(layout.offsets[k0]), int(layout.offsets[k1]), f) for k0, k1, f in _runs(flags)]
+
+
+def _clip(cb: int, ce: int, b: int, e: int) -> Tuple[int, int]:
+    """The range [cb, ce) clipped to the run [b, e), counted from b; (0, 0) where they miss."""
+    lo, hi = max(cb, b), min(ce, e)
+    return (lo - b, hi - b) if lo < hi else (0, 0)
+
+
 NATIVE_PIPELINE = True            # fp32 host mixes above NATIVE_MIN_BYTES of staging: cfa_host_mix_f32
 NATIVE_MIN_BYTES = 1 << 20        # staging bytes from which the native chunk pipeline beats single-shot
 NATIVE_CHUNK_ELEMS = 128 << 10    # elements per model per native pipeline chunk
@@ -130,22 +175,18 @@ class HostMixer:
             s = self._tls.stream = torch.cuda.Stream(self.engine.device)
         return s
 
-    def _upload(self, layout: BucketLayout, arrays) -> torch.Tensor:
-        host = torch.from_numpy(layout.pack(arrays))
-        return host.to(self.engine.device, non_blocking=False)
-
-    def _cached(self, kind: str, n: int, dtype=torch.float32, pinned: bool = False) -> torch.Tensor:
-        """Per-thread cached staging buffer (pinned host or device) of at least n elements."""
+    def _cached(self, kind: str, n: int, pinned: bool = False) -> torch.Tensor:
+        """Per-thread cached fp32 pipeline buffer (pinned host or device) of at least n elements."""
         cache = getattr(self._tls, "bufs", None)
         if cache is None:
             cache = self._tls.bufs = {}
-        t = cache.get((kind, dtype))
+        t = cache.get(kind)
         if t is None or t.numel() < n:
             if pinned:
-                t = torch.empty(max(n, 1), dtype=dtype, pin_memory=True)
+                t = torch.empty(max(n, 1), dtype=torch.float32, pin_memory=True)
             else:
-                t = torch.empty(max(n, 1), dtype=dtype, device=self.engine.device)
-            cache[(kind, dtype)] = t
+                t = torch.empty(max(n, 1), dtype=torch.float32, device=self.engine.device)
+            cache[kind] = t
         return t[:n]
 
     def mix(self, local: Sequence, nbrs: Sequence[Sequence], alphas: Sequence[float],
@@ -165,8 +206,10 @@ class HostMixer:
         pinned staging buffer (rows padded to 16-byte pitch). By default (``SINGLE_ZERO_COPY``)
         the kernel reads those rows over PCIe in place and writes the result into pinned host
         memory: no staging copies, one stream synchronisation; a compression count stays on the
-        device and returns by one 8-byte copy. With ``SINGLE_ZERO_COPY = False`` the staging
-        moves by one async H2D copy and the result by one D2H (same kernels, same results).
+        device and returns by one 8-byte copy (cfa_counter_fetch, which also re-zeroes it). With
+        ``SINGLE_ZERO_COPY = False`` the same rows move by one async H2D copy and the result by
+        one D2H (same kernels, same results). Everything but the pack, the launch and the unpack
+        is prepared once per layout (``_RowPlan``).
         Returns (fp32 arrays with the local shapes, kept count or None).
 
         From NATIVE_MIN_BYTES of staging (without compression or the TF1 rule) the whole host path
@@ -182,109 +225,41 @@ class HostMixer:
                 return self._mix_native(layout, local, nbrs, alphas, divisors), None
             if (n + 1) * P * 4 >= PIPELINE_MIN_BYTES:
                 return self._mix_pipelined(layout, local, nbrs, alphas, divisors), None
-        st = self._stream()
-        if SINGLE_ZERO_COPY:
-            return self._mix_zero_copy(layout, local, nbrs, alphas, divisors, st, compress, tf1)
-        with torch.cuda.stream(st):
-            host = self._cached("h_in", (n + 1) * P, pinned=True)
-            hv = host.numpy().reshape(n + 1, P)
-            layout.pack(local, hv[0])
-            for j, x in enumerate(nbrs):
-                layout.pack(x, hv[j + 1])
-            dev = self._cached("d_in", (n + 1) * P)
-            dev.copy_(host, non_blocking=True)
-            d = dev.view(n + 1, P)
-            out = self._cached("d_out", P)
-            kept = None
-            if tf1:
-                mode, b, e = 0, 0, 0
-                if compress is not None:
-                    mode, layer = compress
-                    b, e = layout.segment(layer)
-                    kept = self._cached("d_cnt", 1, torch.int64)
-                    kept.zero_()
-                self.engine.mix_tf1(out, d[0], list(d[1:]), [float(a) for a in alphas], mode, b, e, kept,
-                                    stream=st)
-            elif compress is not None:
-                mode, layer = compress
-                b, e = layout.segment(layer)
-                kept = self._cached("d_cnt", 1, torch.int64)
-                kept.zero_()
-                self.engine.mix_seq_compress(out, d[0], list(d[1:]), list(alphas), mode, b, e, kept, stream=st)
-            elif divisors is not None:
-                self.engine.mix_seq_div(out, d[0], list(d[1:]), list(alphas), list(divisors), stream=st)
-            else:
-                self.engine.mix_seq(out, d[0], list(d[1:]), list(alphas), stream=st)
-            h_out = self._cached("h_out", P, pinned=True)
-            h_out.copy_(out, non_blocking=True)
-            if kept is not None:
-                h_cnt = self._cached("h_cnt", 1, torch.int64, pinned=True)
-                h_cnt.copy_(kept, non_blocking=True)
-            st.synchronize()
-            flat = h_out.numpy().copy()  # the pinned buffer is reused by the next call
-            kept_n = int(h_cnt.numpy()[0]) if kept is not None else None
-        return layout.unpack(flat, copy=False), kept_n
+        mode, b, e = _compress_range(layout, compress)
+        plan = self._zc_plan("f32", layout, n, np.float32, staged=not SINGLE_ZERO_COPY)
+        plan.pack(local, nbrs)
+        kp = plan.counter if compress is not None else None
+        sh = plan.begin(self._stream())
+        if tf1:
+            plan.launch(plan.lib.cfa_mix_tf1_f32, plan.ob, plan.hb, plan.table, plan.coeffs(alphas, True), n, P,
+                        mode, b, e, kp, sh)
+        elif compress is not None:
+            plan.launch(plan.lib.cfa_mix_seq_compress_f32, plan.ob, plan.hb, plan.table, plan.coeffs(alphas), n, P,
+                        mode, b, e, kp, sh)
+        elif divisors is not None:
+            plan.launch(plan.lib.cfa_mix_seq_div_f32, plan.ob, plan.hb, plan.table, plan.coeffs(alphas),
+                        _lib.float_array(list(divisors)), n, P, sh)
+        else:
+            plan.launch(plan.lib.cfa_mix_seq_f32, plan.ob, plan.hb, plan.table, plan.coeffs(alphas), n, P, sh)
+        kept_n = plan.finish(sh, count=compress is not None)
+        return plan.unpack(), kept_n
 
-    def _zc_plan(self, kind: str, layout: BucketLayout, n: int, dtype, out_dtype=None) -> "_ZeroCopyPlan":
-        """Per-thread cached zero-copy plan for one (kind, layout, fan-in): pinned rows and
-        output, their device addresses and the ctypes tables, built once. ``layout`` is a cached
-        ``_layout_of`` object, so it identifies the layer shapes."""
+    def _zc_plan(self, kind: str, layout: BucketLayout, n: int, dtype, out_dtype=None,
+                 staged: bool = False) -> "_RowPlan":
+        """Per-thread cached row plan for one (kind, layout, fan-in, memory form): pinned rows and
+        output, the addresses the kernels get and the ctypes tables, built once. ``layout`` is a
+        cached ``_layout_of`` object, so it identifies the layer shapes."""
         plans = getattr(self._tls, "plans", None)
         if plans is None:
             plans = self._tls.plans = {}
-        key = (kind, id(layout), n)
+        key = (kind, id(layout), n, staged)
         plan = plans.get(key)
         if plan is None or plan.layout is not layout:
             if len(plans) >= 16:  # bounded: drop the oldest layout
                 plans.pop(next(iter(plans)))
-            plan = plans[key] = _ZeroCopyPlan(self, layout, n, dtype, out_dtype,
-                                              counter=kind not in ("mewma64", "fold64"))
+            plan = plans[key] = _RowPlan(self, layout, n, dtype, out_dtype,
+                                         counter=kind not in ("mewma64", "fold64"), staged=staged)
         return plan
-
-    def _mix_zero_copy(self, layout: BucketLayout, local, nbrs, alphas, divisors, st,
-                       compress=None, tf1=False) -> Tuple[List[np.ndarray], Optional[int]]:
-        """Single-shot fp32 mix without staging copies: the buckets are packed into pinned rows
-        (pitch rounded up to 4 elements, so every row stays 16-byte aligned), the kernel reads
-        them over PCIe and writes the result into pinned host memory; one synchronisation. The
-        compression count (device atomics) stays in device memory and returns by one 8-byte
-        copy (cfa_counter_fetch, which also re-zeroes it). Everything but the pack, the launch
-        and the unpack is prepared once per layout (``_ZeroCopyPlan``)."""
-        n = len(nbrs)
-        plan = self._zc_plan("f32", layout, n, np.float32)
-        plan.pack(local, nbrs)
-        sh = plan.stream_handle(st)
-        lib = plan.lib
-        if tf1 or compress is not None:
-            mode, b, e = 0, 0, 0
-            if compress is not None:
-                mode, layer = compress
-                b, e = layout.segment(layer)
-                if not (0 <= b <= e <= plan.P):
-                    raise ValueError("bad compression layer")
-            kp = plan.counter if compress is not None else None
-            if tf1:
-                rc = lib.cfa_mix_tf1_f32(plan.ob, plan.hb, plan.table, plan.coeffs(alphas, True), n, plan.P,
-                                         int(mode), int(b), int(e), kp, sh)
-                name = "cfa_mix_tf1_f32"
-            else:
-                rc = lib.cfa_mix_seq_compress_f32(plan.ob, plan.hb, plan.table, plan.coeffs(alphas), n, plan.P,
-                                                  int(mode), int(b), int(e), kp, sh)
-                name = "cfa_mix_seq_compress_f32"
-        elif divisors is not None:
-            rc = lib.cfa_mix_seq_div_f32(plan.ob, plan.hb, plan.table, plan.coeffs(alphas),
-                                         _lib.float_array(list(divisors)), n, plan.P, sh)
-            name = "cfa_mix_seq_div_f32"
-        else:
-            rc = lib.cfa_mix_seq_f32(plan.ob, plan.hb, plan.table, plan.coeffs(alphas), n, plan.P, sh)
-            name = "cfa_mix_seq_f32"
-        if rc != _lib.CFA_OK and compress is not None:
-            plan.reset_count()
-        _lib.check(name, rc)
-        if compress is not None:
-            plan.fetch_count(sh)
-        plan.complete(sh)
-        kept_n = int(plan.count_host[0]) if compress is not None else None
-        return plan.unpack(), kept_n
 
     def _aux_streams(self):
         s = getattr(self._tls, "aux", None)
@@ -425,118 +400,54 @@ class HostMixer:
     def compress(self, y: np.ndarray, ref: Optional[np.ndarray], mode: int) -> Tuple[np.ndarray, int]:
         """Standalone compression epilogue (cfa_ongraphs.py:225-273) on one tensor."""
         layout = BucketLayout([np.shape(y)])
+        upload = lambda a: torch.from_numpy(layout.pack([a])).to(self.engine.device)
         with torch.cuda.stream(self._stream()):
-            dy = self._upload(layout, [y])
-            dr = self._upload(layout, [ref]) if ref is not None else None
+            dy = upload(y)
+            dr = upload(ref) if ref is not None else None
             kept = self.engine.counter()
             self.engine.compress(dy, dr, mode, kept, stream=self._stream())
             flat = dy.cpu().numpy()
             n = int(kept.item())
         return flat.reshape(np.shape(y)), n
 
-    def mewma(self, W: Sequence, states: Sequence[np.ndarray], grads: Sequence[Sequence], rho: float,
-              lrs: Sequence[float], init: bool, use_filtered: bool) -> List[np.ndarray]:
-        """CFA-GE update of the per-layer model ``W`` with the neighbours' slot gradients
-        ``grads[j]`` (per-layer arrays) and the per-layer saved-state arrays ``states[k]`` of shape
-        [..., N] (updated IN PLACE at slot j, as the reference does). ``lrs`` = per-layer learning
-        rate; layers with the first rate must precede the others (layer 1 then layer 2)."""
-        layout = _layout_of(W)
-        n = len(grads)
-        first_other = next((k for k in range(len(lrs)) if lrs[k] != lrs[0]), len(lrs))
-        if any(lr != lrs[-1] for lr in lrs[first_other:]):
-            raise ValueError("learning rates must be one value for the leading layers, one for the rest")
-        split = int(layout.offsets[first_other])
-        lr1, lr2 = float(lrs[0]), float(lrs[-1])
-        with torch.cuda.stream(self._stream()):
-            dW = self._upload(layout, W)
-            ds = [self._upload(layout, [np.asarray(st)[..., j] for st in states]) for j in range(n)]
-            dg = [self._upload(layout, g) for g in grads]
-            self.engine.mewma(dW, ds, dg, rho, lr1, lr2, split, init, use_filtered,
-                              stream=self._stream())
-            W_out = dW.cpu().numpy()
-            s_out = [x.cpu().numpy() for x in ds]
-        for j in range(n):
-            for k, arr in enumerate(layout.unpack(s_out[j], copy=False)):
-                states[k][..., j] = arr
-        return layout.unpack(W_out, copy=False)
-
     # -- TF1 on fp64 buckets: the reference's own arithmetic and dtypes -----------------------
-    @staticmethod
-    def _runs(flags):
-        """Maximal runs of consecutive tensors sharing a flag: [(first, last + 1, flag)]."""
-        runs, k = [], 0
-        while k < len(flags):
-            e = k
-            while e < len(flags) and flags[e] == flags[k]:
-                e += 1
-            runs.append((k, e, flags[k]))
-            k = e
-        return runs
-
-    def _upload64(self, layout: BucketLayout, arrays) -> torch.Tensor:
-        host = torch.from_numpy(layout.pack(arrays, np.empty(layout.P, dtype=np.float64)))
-        return host.to(self.engine.device, non_blocking=False)
-
     def mix_tf1(self, local: Sequence, nbrs: Sequence[Sequence], alphas: Sequence[float],
                 compress: Optional[Tuple[int, int]] = None) -> Tuple[List[np.ndarray], Optional[int]]:
         """TF1 mix with the reference's numerics and dtypes (``cfa_mix_tf1_f64``): the arrays are
-        widened to fp64 buckets (exact), folded as numpy 2 folds them (``eps * wf`` is an
-        np.float64: fp32 first subtraction when both operands are fp32 arrays, fp64 after), the
-        compression epilogue of ``compress=(mode, layer)`` applied in fp64; returns the fp64
-        arrays the reference returns, with the local shapes, and the kept count (or None).
+        widened to fp64 rows (exact; an even number of fp64 per row, so 16-byte aligned for odd P
+        too), folded as numpy 2 folds them (``eps * wf`` is an np.float64: fp32 first subtraction
+        when both operands are fp32 arrays, fp64 after), one launch per run of layers with the
+        same step-0 precision, the compression epilogue of ``compress=(mode, layer)`` applied in
+        fp64; returns the fp64 arrays the reference returns, with the local shapes, and the kept
+        count (or None). With ``TF1_ZERO_COPY`` the kernel works on the pinned rows in place, and
+        all-fp32 arrays take ``_mix_tf1_wide``; without it the rows move by one H2D and one D2H.
         Needs at least one neighbour (with none, the reference returns the inputs themselves)."""
         n = len(nbrs)
         if n == 0:
             raise ValueError("mix_tf1 needs at least one neighbour model")
         _check_coefficients(n, alphas)
         layout = _layout_of(local)
-        P = layout.P
         st = self._stream()
-        if TF1_ZERO_COPY:  # fp32 arrays (what TF hands the drivers) take one wide launch
+        staged = not TF1_ZERO_COPY
+        if not staged:  # fp32 arrays (what TF hands the drivers) take one wide launch
             res = self._mix_tf1_wide(layout, local, nbrs, alphas, compress, st)
             if res is not None:
                 return res
+        mode, cb, ce = _compress_range(layout, compress)
         first = nbrs[0]
         flags = tuple(_dtype(local[k]) == _F32 and not callable(first) and _dtype(first[k]) == _F32
                       for k in range(len(local)))
-        if TF1_ZERO_COPY:
-            return self._mix_tf1_zero_copy(layout, local, nbrs, alphas, compress, flags, st)
-        with torch.cuda.stream(st):
-            host = self._cached("h_in64", (n + 1) * P, torch.float64, pinned=True)
-            hv = host.numpy().reshape(n + 1, P)
-            layout.pack(local, hv[0])
-            for j, x in enumerate(nbrs):
-                if callable(x):  # a filler writes the flat bucket itself (e.g. a payload decoder)
-                    x(hv[j + 1])
-                else:
-                    layout.pack(x, hv[j + 1])
-            h_out = self._cached("h_out64", P, torch.float64, pinned=True)
-            dev = self._cached("d_in64", (n + 1) * P, torch.float64)
-            dev.copy_(host, non_blocking=True)
-            d = dev.view(n + 1, P)
-            out = self._cached("d_out64", P, torch.float64)
-            mode, cb, ce, kept = 0, 0, 0, None
-            if compress is not None:
-                mode, layer = compress
-                cb, ce = layout.segment(layer)
-                kept = self._cached("d_cnt", 1, torch.int64)
-                kept.zero_()
-            for k0, k1, f32 in self._runs(flags):  # one launch per run of equal step-0 precision
-                b, e = layout.segment(k0)[0], layout.segment(k1 - 1)[1]
-                lo, hi = max(cb, b), min(ce, e)
-                hit = kept is not None and lo < hi
-                self.engine.mix_tf1_f64(out[b:e], d[0, b:e], [d[j, b:e] for j in range(1, n + 1)],
-                                        [float(a) for a in alphas], f32, mode if hit else 0,
-                                        lo - b if hit else 0, hi - b if hit else 0,
-                                        kept if hit else None, stream=st)
-            h_out.copy_(out, non_blocking=True)
-            if kept is not None:
-                h_cnt = self._cached("h_cnt", 1, torch.int64, pinned=True)
-                h_cnt.copy_(kept, non_blocking=True)
-            st.synchronize()
-            flat = h_out.numpy().copy()
-            kept_n = int(h_cnt.numpy()[0]) if kept is not None else None
-        return layout.unpack(flat, copy=False), kept_n
+        plan = self._zc_plan("f64", layout, n, np.float64, staged=staged)
+        plan.pack(local, nbrs)
+        coeffs = plan.coeffs(alphas, True)
+        sh = plan.begin(st)
+        for b, e, f32 in plan.runs(flags):
+            lo, hi = _clip(cb, ce, b, e)
+            hit = lo < hi
+            plan.launch(plan.lib.cfa_mix_tf1_f64, plan.ob + 8 * b, plan.hb + 8 * b, plan.run_table(b), coeffs, n,
+                        int(f32), e - b, mode if hit else 0, lo, hi, plan.counter if hit else None, sh)
+        kept_n = plan.finish(sh, count=compress is not None)
+        return plan.unpack(), kept_n
 
     def _mix_tf1_wide(self, layout, local, nbrs, alphas, compress, st):
         """mix_tf1 when every array is fp32 (what TF hands the TF1 drivers): fp32 pinned rows, one
@@ -545,138 +456,34 @@ class HostMixer:
         The same values as the fp64-row path (fp32 values widen exactly; step 0 is the fp32
         subtraction there too) at half the packed and PCIe-read bytes."""
         n = len(nbrs)
+        mode, cb, ce = _compress_range(layout, compress)
         plan = self._zc_plan("tf1w", layout, n, np.float32, out_dtype=np.float64)
         if not plan.pack(local, nbrs, require=_F32):
             return None  # some array is not fp32 (or a filler): the fp64-row path takes it
-        sh = plan.stream_handle(st)
-        mode, cb, ce = 0, 0, 0
-        if compress is not None:
-            mode, layer = compress
-            cb, ce = layout.segment(layer)
-        rc = plan.lib.cfa_mix_tf1_wide_f32(plan.ob, plan.hb, plan.table, plan.coeffs(alphas, True), n, plan.P,
-                                           int(mode), int(cb), int(ce),
-                                           plan.counter if compress is not None else None, sh)
-        if rc != _lib.CFA_OK and compress is not None:
-            plan.reset_count()
-        _lib.check("cfa_mix_tf1_wide_f32", rc)
-        if compress is not None:
-            plan.fetch_count(sh)
-        plan.complete(sh)
-        kept_n = int(plan.count_host[0]) if compress is not None else None
+        sh = plan.begin(st)
+        plan.launch(plan.lib.cfa_mix_tf1_wide_f32, plan.ob, plan.hb, plan.table, plan.coeffs(alphas, True), n, plan.P,
+                    mode, cb, ce, plan.counter if compress is not None else None, sh)
+        kept_n = plan.finish(sh, count=compress is not None)
         return plan.unpack(), kept_n
-
-    def _mix_tf1_zero_copy(self, layout, local, nbrs, alphas, compress, flags, st):
-        """mix_tf1 on pinned fp64 rows read and written in place by the kernel (rows of an even
-        number of fp64, so 16-byte aligned for odd P too); one launch per run of layers with
-        the same step-0 precision; the compression count comes back by one 8-byte copy."""
-        n = len(nbrs)
-        plan = self._zc_plan("f64", layout, n, np.float64)
-        plan.pack(local, nbrs)
-        sh = plan.stream_handle(st)
-        mode, cb, ce = 0, 0, 0
-        if compress is not None:
-            mode, layer = compress
-            cb, ce = layout.segment(layer)
-        coeffs = plan.coeffs(alphas, True)
-        for k0, k1, f32 in plan.runs(flags):
-            b, e = layout.segment(k0)[0], layout.segment(k1 - 1)[1]
-            lo, hi = max(cb, b), min(ce, e)
-            hit = compress is not None and lo < hi
-            rc = plan.lib.cfa_mix_tf1_f64(plan.ob + 8 * b, plan.hb + 8 * b, plan.run_table(b), coeffs, n,
-                                          int(bool(f32)), e - b, mode if hit else 0, lo - b if hit else 0,
-                                          hi - b if hit else 0, plan.counter if hit else None, sh)
-            if rc != _lib.CFA_OK:
-                plan.lib.cfa_stream_synchronize(sh)  # earlier runs may still read the pinned rows
-                if compress is not None:
-                    plan.reset_count()
-            _lib.check("cfa_mix_tf1_f64", rc)
-        if compress is not None:
-            plan.fetch_count(sh)
-        plan.complete(sh)
-        kept_n = int(plan.count_host[0]) if compress is not None else None
-        return plan.unpack(), kept_n
-
-    def _mewma_tf1_zero_copy(self, layout, W, states, grads, rho, lr1, lr2, split, init, use_filtered, flags,
-                             st) -> List[np.ndarray]:
-        """mewma_tf1 on pinned fp64 rows updated in place by the kernel over PCIe (row 0 = W,
-        rows 1..n = the saved states' slots, rows n+1..2n = the gradients); one launch per run
-        of layers with equal dtype flags; the states are written back into the caller's arrays
-        at their slots. Returns the W arrays (fp64)."""
-        n = len(grads)
-        layout = _layout_of(W) if layout is None else layout
-        plan = self._zc_plan("mewma64", layout, 2 * n, np.float64)
-        rows = plan.rows
-        sizes = layout.sizes
-        plan.pack(W, [])  # row 0 (the remaining rows are filled below)
-        for j in range(n):
-            for k, v in enumerate(plan.views[1 + j]):
-                np.copyto(v, np.asarray(states[k])[..., j].reshape(-1), casting="unsafe")
-            g = grads[j]
-            for k, v in enumerate(plan.views[1 + n + j]):
-                a = np.asarray(g[k])
-                if a.size != sizes[k]:
-                    raise ValueError(f"gradient {j} tensor {k} has {a.size} elements, layout expects {sizes[k]}")
-                np.copyto(v, a.reshape(-1), casting="unsafe")
-        sh = plan.stream_handle(st)
-        ones = plan.strides_one()
-        for k0, k1, mask in plan.runs(tuple(flags)):
-            b, e = layout.segment(k0)[0], layout.segment(k1 - 1)[1]
-            rc = plan.lib.cfa_mewma_tf1_f64(plan.hb + 8 * b, plan.row_table(1, n, b), plan.row_table(1 + n, n, b),
-                                            ones, n, float(rho), float(lr1), float(lr2), max(0, min(split, e) - b),
-                                            int(bool(init)), int(bool(use_filtered)), int(mask), e - b, sh)
-            if rc != _lib.CFA_OK:
-                plan.lib.cfa_stream_synchronize(sh)  # earlier runs may still update the pinned rows
-            _lib.check("cfa_mewma_tf1_f64", rc)
-        plan.complete(sh)
-        for j in range(n):
-            for k, v in enumerate(plan.views[1 + j]):
-                states[k][..., j] = v.reshape(layout.shapes[k])
-        P = layout.P
-        flat = rows[0, :P].copy()
-        return [flat[b:e].reshape(shp) for (b, e), shp in
-                zip((layout.segment(k) for k in range(len(sizes))), layout.shapes)]
 
     def fold64(self, local: Sequence, nbrs: Sequence[Sequence], alphas: Sequence[float], rule: int,
                divisors: Optional[Sequence[float]] = None) -> List[np.ndarray]:
-        """fp64 fold (``cfa_fold_f64``) of per-layer arrays widened to fp64 buckets; returns fp64
+        """fp64 fold (``cfa_fold_f64``) of per-layer arrays widened to fp64 rows; returns fp64
         arrays with the local shapes. By default (``TF1_ZERO_COPY``) the kernel reads the pinned
-        rows and writes the pinned output in place; otherwise one H2D of all buckets, one launch,
-        one D2H. A neighbour
-        may be given as a callable ``fill(dst)`` that writes its flat fp64 bucket into the pinned
-        staging row ``dst`` (the MQTT payload decoder does)."""
+        rows and writes the pinned output in place; otherwise one H2D of all rows, the same
+        launch, one D2H. A neighbour may be given as a callable ``fill(dst)`` that writes its flat
+        fp64 bucket into the pinned staging row ``dst`` (the MQTT payload decoder does)."""
         layout = _layout_of(local)
         P, n = layout.P, len(nbrs)
         _check_coefficients(n, alphas, divisors if rule == _lib.RULE_SEQUENTIAL_DIV else None)
-        st = self._stream()
-        if TF1_ZERO_COPY:  # the kernel reads the pinned fp64 rows and writes the pinned output in place
-            plan = self._zc_plan("fold64", layout, n, np.float64)
-            plan.pack(local, nbrs)
-            sh = plan.stream_handle(st)
-            div = _lib.double_array([float(x) for x in divisors]) if divisors is not None else None
-            _lib.check("cfa_fold_f64", plan.lib.cfa_fold_f64(plan.ob, plan.hb, plan.table, plan.coeffs(alphas, True),
-                                                             div, n, int(rule), P, sh))
-            plan.complete(sh)
-            return plan.unpack()
-        with torch.cuda.stream(st):
-            host = self._cached("h_in64", (n + 1) * P, torch.float64, pinned=True)
-            hv = host.numpy().reshape(n + 1, P)
-            layout.pack(local, hv[0])
-            for j, x in enumerate(nbrs):
-                if callable(x):  # a filler writes the flat bucket itself (e.g. a payload decoder)
-                    x(hv[j + 1])
-                else:
-                    layout.pack(x, hv[j + 1])
-            dev = self._cached("d_in64", (n + 1) * P, torch.float64)
-            dev.copy_(host, non_blocking=True)
-            d = dev.view(n + 1, P)
-            out = self._cached("d_out64", P, torch.float64)
-            self.engine.fold_f64(out, d[0], [d[j] for j in range(1, n + 1)], [float(a) for a in alphas], rule,
-                                 None if divisors is None else [float(x) for x in divisors], stream=st)
-            h_out = self._cached("h_out64", P, torch.float64, pinned=True)
-            h_out.copy_(out, non_blocking=True)
-            st.synchronize()
-            flat = h_out.numpy().copy()
-        return layout.unpack(flat, copy=False)
+        plan = self._zc_plan("fold64", layout, n, np.float64, staged=not TF1_ZERO_COPY)
+        plan.pack(local, nbrs)
+        div = _lib.double_array([float(x) for x in divisors]) if divisors is not None else None
+        sh = plan.begin(self._stream())
+        plan.launch(plan.lib.cfa_fold_f64, plan.ob, plan.hb, plan.table, plan.coeffs(alphas, True), div, n, int(rule),
+                    P, sh)
+        plan.finish(sh)
+        return plan.unpack()
 
     def mewma_tf1(self, W: Sequence, states: Sequence[np.ndarray], grads: Sequence[Sequence], rho: float,
                   lrs: Sequence[float], init: bool, use_filtered: bool) -> List[np.ndarray]:
@@ -685,58 +492,62 @@ class HostMixer:
         arrays ``states[k]`` [..., N] updated IN PLACE at slot j in their own dtype. Every
         operation is promoted as numpy 2 promotes it for the arrays' dtypes (Python-float rho and
         learning rates), so the result is the reference's: fp64 model arrays for its fp64
-        gradients. ``lrs`` as in ``mewma``."""
+        gradients. ``lrs`` = per-layer learning rate; layers with the first rate must precede the
+        others (layer 1 then layer 2).
+
+        The fp64 rows (row 0 = W, rows 1..n = the saved states' slots, rows n+1..2n = the
+        gradients) are updated in place by the kernel, over PCIe by default (``TF1_ZERO_COPY``)
+        or in their device mirror; one launch per run of layers with equal dtype flags."""
         layout = _layout_of(W)
         n = len(grads)
-        first_other = next((k for k in range(len(lrs)) if lrs[k] != lrs[0]), len(lrs))
-        if any(lr != lrs[-1] for lr in lrs[first_other:]):
-            raise ValueError("learning rates must be one value for the leading layers, one for the rest")
-        split = int(layout.offsets[first_other])
-        lr1, lr2 = float(lrs[0]), float(lrs[-1])
+        lr1, lr2, split = _lr_split(layout, lrs)
         from ..engine import TF1_GRAD_F32, TF1_STATE_F32, TF1_W_F32
         f32 = lambda a: _dtype(a) == _F32
+        if n == 0:  # no update comes, nothing is launched: W as it is, an fp32 tensor staying fp32
+            return [np.asarray(w).astype(np.float32 if f32(w) else np.float64) for w in W]
         gf = [[f32(g[k]) for g in grads] for k in range(len(W))]
-        flags = [(TF1_STATE_F32 if f32(states[k]) else 0) | (TF1_W_F32 if f32(W[k]) else 0)
-                 | (TF1_GRAD_F32 if n and all(gf[k]) else 0) for k in range(len(W))]
-        if n and any(len(set(gf[k])) > 1 for k in range(len(W))):
+        flags = tuple((TF1_STATE_F32 if f32(states[k]) else 0) | (TF1_W_F32 if f32(W[k]) else 0)
+                      | (TF1_GRAD_F32 if all(gf[k]) else 0) for k in range(len(W)))
+        if any(len(set(gf[k])) > 1 for k in range(len(W))):
             raise ValueError("neighbour gradients of one layer must share a dtype")
-        st_ = self._stream()
-        if TF1_ZERO_COPY and n > 0:
-            W_out = self._mewma_tf1_zero_copy(layout, W, states, grads, rho, lr1, lr2, split, init, use_filtered,
-                                              flags, st_)
-            u32 = lambda k: bool(flags[k] & (TF1_STATE_F32 if use_filtered else TF1_GRAD_F32))
-            return [w.astype(np.float32) if (flags[k] & TF1_W_F32 and u32(k)) and f32(W[k]) else w
-                    for k, w in enumerate(W_out)]
-        with torch.cuda.stream(st_):
-            dW = self._upload64(layout, W)
-            ds = [self._upload64(layout, [np.asarray(st)[..., j] for st in states]) for j in range(n)]
-            dg = [self._upload64(layout, g) for g in grads]
-            for k0, k1, mask in self._runs(flags):
-                b, e = layout.segment(k0)[0], layout.segment(k1 - 1)[1]
-                self.engine.mewma_tf1_f64(dW[b:e], [x[b:e] for x in ds], [x[b:e] for x in dg], rho, lr1, lr2,
-                                          max(0, min(split, e) - b), init, use_filtered, mask, stream=st_)
-            W_out = dW.cpu().numpy()
-            s_out = [x.cpu().numpy() for x in ds]
+        plan = self._zc_plan("mewma64", layout, 2 * n, np.float64, staged=not TF1_ZERO_COPY)
+        plan.pack(W, [[np.asarray(s)[..., j] for s in states] for j in range(n)])
         for j in range(n):
-            for k, arr in enumerate(layout.unpack(s_out[j], copy=False)):
-                states[k][..., j] = arr
-        # a model tensor stays fp32 only while every update it receives is fp32 (or none comes)
+            plan.pack(grads[j], (), first=1 + n + j, what=f"gradient {j} tensor")
+        ones = plan.strides_one()
+        sh = plan.begin(self._stream())
+        for b, e, mask in plan.runs(flags):
+            plan.launch(plan.lib.cfa_mewma_tf1_f64, plan.hb + 8 * b, plan.row_table(1, n, b), plan.row_table(1 + n, n, b),
+                        ones, n, float(rho), lr1, lr2, max(0, min(split, e) - b), int(bool(init)),
+                        int(bool(use_filtered)), int(mask), e - b, sh)
+        plan.finish(sh, inplace_rows=1 + n)
+        for j in range(n):  # the states go back into the caller's arrays at their slots
+            for k, v in enumerate(plan.shaped_views[1 + j]):
+                states[k][..., j] = v
+        # a model tensor stays fp32 only while every update it receives is fp32
         u32 = lambda k: bool(flags[k] & (TF1_STATE_F32 if use_filtered else TF1_GRAD_F32))
-        return [w.astype(np.float32) if (n == 0 or (flags[k] & TF1_W_F32 and u32(k))) and f32(W[k]) else w
-                for k, w in enumerate(layout.unpack(W_out, copy=False))]
+        return [w.astype(np.float32) if (flags[k] & TF1_W_F32 and u32(k)) and f32(W[k]) else w
+                for k, w in enumerate(plan.unpack(row=0))]
 
 
-class _ZeroCopyPlan:
-    """Reusable zero-copy state of one layout and fan-in on one thread (see HostMixer._zc_plan).
+class _RowPlan:
+    """Reusable rows of one layout and fan-in on one thread (see HostMixer._zc_plan), in one of
+    two memory forms.
 
     Rows of ``pitch`` elements (16-byte multiples) in one pinned buffer: row 0 the local model,
-    rows 1..n the neighbours; the output is a separate pinned row. The kernel reads and writes
-    them through their device addresses over PCIe. ``views[m][k]`` is layer k of row m (flat),
-    so a pack is one ``np.copyto`` per layer, with the same dtype conversion as
-    ``BucketLayout.pack``."""
+    rows 1..n the neighbours; the output is a separate pinned row. ``views[m][k]`` is layer k of
+    row m (flat), so a pack is one ``np.copyto`` per layer, with the same dtype conversion as
+    ``BucketLayout.pack``.
+
+    Mapped (the default): ``hb`` and ``ob`` are the device addresses of the pinned rows and the
+    pinned output, which the kernel reads and writes over PCIe; a call ends in ``complete``.
+    Staged: ``hb`` and ``ob`` are a device mirror of the rows and a device output of the same
+    pitch; ``begin`` enqueues one H2D copy of the packed rows, ``finish`` the D2H copies and a
+    hipStreamSynchronize. The operations are written once against ``hb``, ``ob`` and the tables
+    made from them, and differ between the forms in nothing else."""
 
     def __init__(self, mixer: "HostMixer", layout: BucketLayout, n: int, dtype, out_dtype=None,
-                 counter: bool = True):
+                 counter: bool = True, staged: bool = False):
         self.layout = layout
         shapes = layout.shapes
         self.P, self.n = self.layout.P, n
@@ -754,15 +565,21 @@ class _ZeroCopyPlan:
         self.out_np = self.out.numpy()[:self.P]
         self.out_slices = [(slice(b, e), shp) for (b, e), shp in zip(segs, self.layout.shapes)]
         eng = mixer.engine
-        self.hb, self.ob = eng.host_device_ptr(self.host), eng.host_device_ptr(self.out)
+        self.lib = _lib.load()
+        self.staged = staged
+        if staged:
+            self.dev = torch.empty(self.host.numel(), dtype=self.host.dtype, device=eng.device)
+            self.dev_out = torch.empty(max(self.pitch, 1), dtype=self.out.dtype, device=eng.device)
+            self.hb, self.ob = self.dev.data_ptr(), self.dev_out.data_ptr()
+        else:
+            self.hb, self.ob = eng.host_device_ptr(self.host), eng.host_device_ptr(self.out)
+            # completion word (cfa_stream_signal / cfa_wait_signal): one pinned 32-bit word per
+            # plan, i.e. per thread and layout, set by the GPU to the call's sequence number
+            self.sig_t = torch.zeros(16, dtype=torch.int32, pin_memory=True)
+            self.sig_host, self.sig_dev = self.sig_t.data_ptr(), eng.host_device_ptr(self.sig_t)
+            self.seq = 0
         isz = self.dtype.itemsize
         self.table = _lib.ptr_table([self.hb + isz * self.pitch * (j + 1) for j in range(n)])
-        self.lib = _lib.load()
-        # completion word (cfa_stream_signal / cfa_wait_signal): one pinned 32-bit word per plan,
-        # i.e. per thread and layout, set by the GPU to the call's sequence number
-        self.sig_t = torch.zeros(16, dtype=torch.int32, pin_memory=True)
-        self.sig_host, self.sig_dev = self.sig_t.data_ptr(), eng.host_device_ptr(self.sig_t)
-        self.seq = 0
         self._coeffs = {}
         self._tables = {}
         self._runs = {}
@@ -773,29 +590,65 @@ class _ZeroCopyPlan:
         self.counter_t = self.counter = self.count_pinned = self.count_host = None
         if counter:
             self.counter_t = torch.zeros(1, dtype=torch.int64, device=eng.device)
-            torch.cuda.current_stream(eng.device).synchronize()
             self.counter = self.counter_t.data_ptr()
             self.count_pinned = torch.zeros(1, dtype=torch.int64, pin_memory=True)
             self.count_host = self.count_pinned.numpy()
+        if counter or staged:  # torch made them on its current stream; the calls use the mixer's
+            torch.cuda.current_stream(eng.device).synchronize()
 
-    def complete(self, sh: int) -> None:
-        """Waits until the plan's work on stream ``sh`` is done. With ``SIGNAL_COMPLETION`` a
-        one-lane kernel after the work stores this call's sequence number into the plan's pinned
-        word and the host spins on it (``cfa_wait_signal``): 17.0 -> 13.5 us per C1 call against
-        hipStreamSynchronize's wake-up (``tools/probe/flag_sync.py``,
-        ``profiles/r03v_flag_sync.jsonl``). Without the word after ``SIGNAL_SPIN_US`` the wait
-        falls back to hipStreamSynchronize, which also reports an error of the stream's work."""
-        if not SIGNAL_COMPLETION:
-            _lib.check("cfa_stream_synchronize", self.lib.cfa_stream_synchronize(sh))
-            return
-        self.seq = self.seq % 0xFFFFFFFF + 1
-        _lib.check("cfa_stream_signal", self.lib.cfa_stream_signal(self.sig_dev, self.seq, sh))
-        _lib.check("cfa_wait_signal", self.lib.cfa_wait_signal(self.sig_host, self.seq, sh, SIGNAL_SPIN_US))
-
-    def stream_handle(self, st) -> int:
+    def begin(self, st) -> int:
+        """Before the launches, once the rows are packed: returns the handle of stream ``st`` for
+        them; the staged form first enqueues the H2D copy of the rows on it."""
         if self._sh is None or self._sh[0] is not st:
             self._sh = (st, int(st.cuda_stream))
-        return self._sh[1]
+        sh = self._sh[1]
+        if self.staged:
+            _lib.check("cfa_memcpy_async", self.lib.cfa_memcpy_async(
+                self.hb, self.host.data_ptr(), (self.n + 1) * self.pitch * self.dtype.itemsize, sh))
+        return sh
+
+    def launch(self, fn, *args) -> None:
+        """One libcfa entry point by raw pointer (its last argument is the stream). On failure:
+        synchronize the stream (the copy and the earlier launches of this call may still use the
+        rows), zero a counter that may hold a partial sum, and raise."""
+        rc = fn(*args)
+        if rc != _lib.CFA_OK:
+            msg = self.lib.cfa_last_error()  # before the clean-up calls can replace it
+            self.lib.cfa_stream_synchronize(args[-1])
+            if self.counter_t is not None:
+                self.counter_t.zero_()
+                torch.cuda.synchronize(self.counter_t.device)
+            raise _lib.CFAError(fn.__name__, rc, msg.decode() if msg else "")
+
+    def finish(self, sh: int, count: bool = False, inplace_rows: int = 0) -> Optional[int]:
+        """After the launches: returns once the results are in the pinned output, or, for a kind
+        that updates its rows in place, in the first ``inplace_rows`` pinned rows. ``count``: the
+        compression count too, which is returned; the device counter's value goes into
+        ``count_host`` and the counter is reset in stream order (cfa_counter_fetch).
+
+        The staged form enqueues the D2H copy of the output, or of those rows, and calls
+        hipStreamSynchronize; it never uses the completion word. The mapped form only waits. With
+        ``SIGNAL_COMPLETION`` a one-lane kernel after the work stores this call's sequence number
+        into the plan's pinned word and the host spins on it (``cfa_wait_signal``): 17.0 -> 13.5 us
+        per C1 call against hipStreamSynchronize's wake-up (``tools/probe/flag_sync.py``,
+        ``profiles/r03v_flag_sync.jsonl``). Without the word after ``SIGNAL_SPIN_US`` the wait
+        falls back to hipStreamSynchronize, which also reports an error of the stream's work."""
+        lib = self.lib
+        if count:
+            _lib.check("cfa_counter_fetch", lib.cfa_counter_fetch(self.counter, self.count_pinned.data_ptr(), sh))
+        if self.staged:
+            if inplace_rows:
+                dst, src, nbytes = self.host.data_ptr(), self.hb, inplace_rows * self.pitch * self.dtype.itemsize
+            else:
+                dst, src, nbytes = self.out.data_ptr(), self.ob, self.P * self.out.element_size()
+            _lib.check("cfa_memcpy_async", lib.cfa_memcpy_async(dst, src, nbytes, sh))
+        if self.staged or not SIGNAL_COMPLETION:
+            _lib.check("cfa_stream_synchronize", lib.cfa_stream_synchronize(sh))
+        else:
+            self.seq = self.seq % 0xFFFFFFFF + 1
+            _lib.check("cfa_stream_signal", lib.cfa_stream_signal(self.sig_dev, self.seq, sh))
+            _lib.check("cfa_wait_signal", lib.cfa_wait_signal(self.sig_host, self.seq, sh, SIGNAL_SPIN_US))
+        return int(self.count_host[0]) if count else None
 
     def coeffs(self, alphas, f64: bool = False):
         key = (tuple(alphas), f64)
@@ -808,24 +661,19 @@ class _ZeroCopyPlan:
         return arr
 
     def runs(self, flags: tuple):
-        """HostMixer._runs(flags), cached per flag pattern."""
+        """_run_bounds(layout, flags), cached per flag pattern."""
         r = self._runs.get(flags)
         if r is None:
-            r = self._runs[flags] = HostMixer._runs(list(flags))
+            r = self._runs[flags] = _run_bounds(self.layout, flags)
         return r
 
     def run_table(self, b: int):
         """Neighbour pointer table of the element offset ``b`` (one launch per dtype run)."""
-        t = self._tables.get(b)
-        if t is None:
-            isz = self.dtype.itemsize
-            t = self._tables[b] = _lib.ptr_table([self.hb + isz * (self.pitch * (j + 1) + b)
-                                                  for j in range(self.n)])
-        return t
+        return self.row_table(1, self.n, b)
 
     def row_table(self, first: int, count: int, b: int):
         """Pointer table of rows first..first+count-1 at element offset ``b`` (cached)."""
-        key = ("rows", first, count, b)
+        key = (first, count, b)
         t = self._tables.get(key)
         if t is None:
             isz = self.dtype.itemsize
@@ -839,12 +687,13 @@ class _ZeroCopyPlan:
             t = self._tables["ones"] = _lib.int64_array([1] * max(1, self.n))
         return t
 
-    def pack(self, local, nbrs, require=None) -> bool:
-        """Copy every model into its row (converting dtypes). With ``require`` (a dtype), stop and
-        return False at the first array of another dtype or at a filler; True when packed."""
+    def pack(self, local, nbrs, require=None, first: int = 0, what: str = "tensor") -> bool:
+        """Copy every model into its row, from row ``first`` on (converting dtypes). With
+        ``require`` (a dtype), stop and return False at the first array of another dtype or at a
+        filler; True when packed. ``what`` names the arrays in a size error."""
         sizes, shapes = self.layout.sizes, self.layout.shapes
         shaped = self.shaped_views
-        for m, model in enumerate((local, *nbrs)):
+        for m, model in enumerate((local, *nbrs), first):
             if callable(model):  # a filler writes the flat bucket itself (e.g. a payload decoder)
                 if require is not None:
                     return False
@@ -862,22 +711,14 @@ class _ZeroCopyPlan:
                 if require is not None and a.dtype != require:
                     return False
                 if a.size != sizes[k]:
-                    raise ValueError(f"tensor {k} has {a.size} elements, layout expects {sizes[k]}")
+                    raise ValueError(f"{what} {k} has {a.size} elements, layout expects {sizes[k]}")
                 np.copyto(self.views[m][k], a.reshape(-1), casting="unsafe")
         return True
 
-    def fetch_count(self, sh: int) -> None:
-        """Stream-ordered: the device counter's value into ``count_host`` and the counter reset
-        (cfa_counter_fetch); the value is valid after the stream synchronisation."""
-        _lib.check("cfa_counter_fetch", self.lib.cfa_counter_fetch(self.counter, self.count_pinned.data_ptr(), sh))
-
-    def reset_count(self) -> None:
-        """After a failed call: the counter may hold a partial sum; zero it (synchronously)."""
-        self.counter_t.zero_()
-        torch.cuda.synchronize(self.counter_t.device)
-
-    def unpack(self) -> List[np.ndarray]:
-        flat = self.out_np.copy()  # the pinned row is reused by the next call
+    def unpack(self, row: Optional[int] = None) -> List[np.ndarray]:
+        """The output (or, for a kind that updates its rows in place, row ``row``) as per-layer
+        arrays; a copy, since the pinned memory is reused by the next call."""
+        flat = (self.out_np if row is None else self.rows[row, :self.P]).copy()
         return [flat[sl].reshape(shp) for sl, shp in self.out_slices]
 
 

@@ -50,6 +50,41 @@ def _check_bucket(t: torch.Tensor, name: str, P: Optional[int] = None, dtype=tor
     return n
 
 
+def _check_fanin(out: torch.Tensor, local: torch.Tensor, nbrs, dtype=torch.float32) -> int:
+    """The buckets of one fold: ``local``, ``out`` and every neighbour, all of local's P elements."""
+    P = _check_bucket(local, "local", dtype=dtype)
+    _check_bucket(out, "out", P, dtype)
+    for j, x in enumerate(nbrs):
+        _check_bucket(x, f"nbrs[{j}]", P, dtype)
+    return P
+
+
+_FP = {torch.float32: "fp32", torch.float64: "fp64"}
+
+
+def _check_mewma(W: torch.Tensor, s, g, dtype) -> tuple:
+    """The buckets of a MEWMA update: ``W`` and one state bucket per gradient, which may be an
+    element-strided 1-D view. Returns (P, the gradients' element strides)."""
+    P = _check_bucket(W, "W", dtype=dtype)
+    if len(s) != len(g):
+        raise ValueError("one state bucket per gradient bucket")
+    strides = []
+    for j in range(len(g)):
+        _check_bucket(s[j], f"s[{j}]", P, dtype)
+        gj = g[j]
+        if not gj.is_cuda or gj.dtype != dtype or gj.dim() != 1 or gj.numel() != P:
+            raise ValueError(f"g[{j}] must be a 1-D {_FP[dtype]} CUDA view of {P} elements")
+        strides.append(int(gj.stride(0)))
+    return P, strides
+
+
+def _check_tables(*tables) -> None:
+    """Device tables, each given as (name, tensor, dtype)."""
+    for name, t, dt in tables:
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise TypeError(f"{name} must be a contiguous {dt} CUDA tensor")
+
+
 def _foreign(objs, index: int):
     """The first CUDA tensor or stream in ``objs`` (tensors, streams, and lists / tuples of them)
     that is not on GPU ``index``, else None."""
@@ -76,11 +111,20 @@ def _same_device(fn):
     return checked
 
 
+def _check_nd(t: torch.Tensor, name: str, nd: int = 2, what: Optional[str] = None, pitched: bool = False) -> tuple:
+    """Shape of an fp32 CUDA tensor of ``nd`` dimensions that is contiguous (named ``what`` in
+    the error, by default "nd-D") or, ``pitched``, has unit element stride and any row pitch."""
+    ok = isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == nd
+    if pitched:
+        if not ok or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise TypeError(f"{name} must be a {nd}-D fp32 CUDA tensor with unit element stride")
+    elif not ok or not t.is_contiguous():
+        raise TypeError(f"{name} must be a contiguous {what or f'{nd}-D'} fp32 CUDA tensor")
+    return tuple(int(d) for d in t.shape)
+
+
 def _check_2d(t: torch.Tensor, name: str):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 \
-            or not t.is_contiguous():
-        raise TypeError(f"{name} must be a contiguous 2-D fp32 CUDA tensor")
-    return int(t.shape[0]), int(t.shape[1])
+    return _check_nd(t, name)
 
 
 TF1_STATE_F32, TF1_GRAD_F32, TF1_W_F32 = 1, 2, 4  # cfa_mewma_tf1_f64 dtype mask
@@ -152,10 +196,7 @@ class Engine:
                 alphas: Sequence[float], stream=None, launch: Optional[tuple] = None) -> torch.Tensor:
         """out = fold_j(w <- w + alphas[j]*(nbrs[j] - w)), w0 = local (sequential CFA rule).
         ``launch`` = (blocks_per_cu, vec_per_lane, nontemporal) overrides the launch shape."""
-        P = _check_bucket(local, "local")
-        _check_bucket(out, "out", P)
-        for j, x in enumerate(nbrs):
-            _check_bucket(x, f"nbrs[{j}]", P)
+        P = _check_fanin(out, local, nbrs)
         if len(alphas) != len(nbrs):
             raise ValueError("one alpha per neighbour required")
         table = _lib.ptr_table([x.data_ptr() for x in nbrs])
@@ -175,10 +216,7 @@ class Engine:
         which enqueues the same kernel with one foreign call. For rounds that repeat the same
         mixes on resident buffers (population shards), where per-launch Python work would
         otherwise approach the kernel time at small buckets. The tensors must stay alive."""
-        P = _check_bucket(local, "local")
-        _check_bucket(out, "out", P)
-        for j, x in enumerate(nbrs):
-            _check_bucket(x, f"nbrs[{j}]", P)
+        P = _check_fanin(out, local, nbrs)
         if len(alphas) != len(nbrs):
             raise ValueError("one alpha per neighbour required")
         table = _lib.ptr_table([x.data_ptr() for x in nbrs])
@@ -231,10 +269,7 @@ class Engine:
     def mix_seq_div(self, out: torch.Tensor, local: torch.Tensor, nbrs: Sequence[torch.Tensor],
                     alphas: Sequence[float], divisors: Sequence[float], stream=None) -> torch.Tensor:
         """out = fold_j(w <- w + (alphas[j]*(nbrs[j] - w)) / divisors[j]) (FedAvg form)."""
-        P = _check_bucket(local, "local")
-        _check_bucket(out, "out", P)
-        for j, x in enumerate(nbrs):
-            _check_bucket(x, f"nbrs[{j}]", P)
+        P = _check_fanin(out, local, nbrs)
         if not (len(alphas) == len(divisors) == len(nbrs)):
             raise ValueError("one alpha and one divisor per neighbour required")
         _lib.call("cfa_mix_seq_div_f32", out.data_ptr(), local.data_ptr(),
@@ -245,10 +280,7 @@ class Engine:
     def mix_linear(self, out: torch.Tensor, local: torch.Tensor, nbrs: Sequence[torch.Tensor],
                    coeff: Sequence[float], stream=None) -> torch.Tensor:
         """out = coeff[0]*local + sum_j coeff[j+1]*nbrs[j]."""
-        P = _check_bucket(local, "local")
-        _check_bucket(out, "out", P)
-        for j, x in enumerate(nbrs):
-            _check_bucket(x, f"nbrs[{j}]", P)
+        P = _check_fanin(out, local, nbrs)
         if len(coeff) != len(nbrs) + 1:
             raise ValueError("len(coeff) must be len(nbrs) + 1")
         _lib.call("cfa_mix_f32", out.data_ptr(), local.data_ptr(),
@@ -261,10 +293,7 @@ class Engine:
                          cbegin: int, cend: int, kept: torch.Tensor, stream=None) -> torch.Tensor:
         """Sequential mix fused with the cfa_ongraphs compression epilogue on [cbegin, cend).
         Adds the kept-parameter count to ``kept`` (int64 CUDA tensor of one element)."""
-        P = _check_bucket(local, "local")
-        _check_bucket(out, "out", P)
-        for j, x in enumerate(nbrs):
-            _check_bucket(x, f"nbrs[{j}]", P)
+        P = _check_fanin(out, local, nbrs)
         self._check_counter(kept)
         if len(alphas) != len(nbrs):
             raise ValueError("one alpha per neighbour required")
@@ -281,10 +310,7 @@ class Engine:
         fp64 compression epilogue on [cbegin, cend), one rounding to fp32). ``alphas`` are the
         float64 products eps * wf_j. ``kept`` (int64 CUDA tensor of one element) is required
         when ``mode`` != 0."""
-        P = _check_bucket(local, "local")
-        _check_bucket(out, "out", P)
-        for j, x in enumerate(nbrs):
-            _check_bucket(x, f"nbrs[{j}]", P)
+        P = _check_fanin(out, local, nbrs)
         if kept is not None:
             self._check_counter(kept)
         if len(alphas) != len(nbrs):
@@ -310,11 +336,7 @@ class Engine:
                     cend: int = 0, kept: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
         """TF1 mix on fp64 buckets (cfa_mix_tf1_f64): the reference's fp64 chain, unrounded.
         ``step0_f32``: the reference's local and first-neighbour arrays are both fp32."""
-        F64 = torch.float64
-        P = _check_bucket(local, "local", dtype=F64)
-        _check_bucket(out, "out", P, F64)
-        for j, x in enumerate(nbrs):
-            _check_bucket(x, f"nbrs[{j}]", P, F64)
+        P = _check_fanin(out, local, nbrs, torch.float64)
         if kept is not None:
             self._check_counter(kept)
         if len(alphas) != len(nbrs):
@@ -329,11 +351,7 @@ class Engine:
                  alphas: Sequence[float], rule: int, divisors: Optional[Sequence[float]] = None,
                  stream=None) -> torch.Tensor:
         """fp64 fold (cfa_fold_f64): SEQUENTIAL, SEQUENTIAL_DIV (``divisors``) or ACCUMULATE."""
-        F64 = torch.float64
-        P = _check_bucket(local, "local", dtype=F64)
-        _check_bucket(out, "out", P, F64)
-        for j, x in enumerate(nbrs):
-            _check_bucket(x, f"nbrs[{j}]", P, F64)
+        P = _check_fanin(out, local, nbrs, torch.float64)
         if len(alphas) != len(nbrs) or (divisors is not None and len(divisors) != len(nbrs)):
             raise ValueError("one alpha (and one divisor, when given) per neighbour required")
         _lib.call("cfa_fold_f64", out.data_ptr(), local.data_ptr(),
@@ -348,17 +366,7 @@ class Engine:
         """CFA-GE MEWMA on fp64 buckets (cfa_mewma_tf1_f64); W and s_j in place. ``g`` may be
         element-strided 1-D fp64 views. ``f32_mask``: which reference arrays are fp32
         (TF1_STATE_F32 | TF1_GRAD_F32 | TF1_W_F32)."""
-        F64 = torch.float64
-        P = _check_bucket(W, "W", dtype=F64)
-        if len(s) != len(g):
-            raise ValueError("one state bucket per gradient bucket")
-        strides = []
-        for j in range(len(g)):
-            _check_bucket(s[j], f"s[{j}]", P, F64)
-            gj = g[j]
-            if not gj.is_cuda or gj.dtype != F64 or gj.dim() != 1 or gj.numel() != P:
-                raise ValueError(f"g[{j}] must be a 1-D fp64 CUDA view of {P} elements")
-            strides.append(int(gj.stride(0)))
+        P, strides = _check_mewma(W, s, g, torch.float64)
         _lib.call("cfa_mewma_tf1_f64", W.data_ptr(), _lib.ptr_table([x.data_ptr() for x in s]),
                   _lib.ptr_table([x.data_ptr() for x in g]), _lib.int64_array(strides), len(g),
                   float(rho), float(lr1), float(lr2), int(lr_split), int(bool(init)),
@@ -387,16 +395,7 @@ class Engine:
               stream=None) -> torch.Tensor:
         """CFA-GE update: for each j, s_j <- init ? g_j : rho*g_j + (1-rho)*s_j;
         W <- W - lr*(use_filtered ? s_j : g_j) with lr = lr1 below lr_split, lr2 above."""
-        P = _check_bucket(W, "W")
-        if len(s) != len(g):
-            raise ValueError("one state bucket per gradient bucket")
-        strides = []
-        for j in range(len(g)):
-            _check_bucket(s[j], f"s[{j}]", P)
-            gj = g[j]
-            if not gj.is_cuda or gj.dtype != torch.float32 or gj.dim() != 1 or gj.numel() != P:
-                raise ValueError(f"g[{j}] must be a 1-D fp32 CUDA view of {P} elements")
-            strides.append(int(gj.stride(0)))
+        P, strides = _check_mewma(W, s, g, torch.float32)
         _lib.call("cfa_mewma_update_f32", W.data_ptr(), _lib.ptr_table([x.data_ptr() for x in s]),
                   _lib.ptr_table([x.data_ptr() for x in g]), _lib.int64_array(strides), len(g),
                   float(rho), float(lr1), float(lr2), int(lr_split), int(bool(init)),
@@ -456,15 +455,14 @@ class Engine:
         ``workspace`` (``grad_workspace``) lets each evaluation's batch spread over workgroups.
         ``grads=None``: partials only, [M][grad_splits(M, B, P)][P] into ``workspace`` (at least
         that size), summed later by ``ge_population_step(..., reduce=...)``."""
-        for name, t, nd in (("x", x, 3), ("y", y, 3)):
-            if not t.is_cuda or t.dtype != torch.float32 or t.dim() != nd or not t.is_contiguous():
-                raise TypeError(f"{name} must be a contiguous 3-D fp32 CUDA tensor")
+        Dx, B, L = _check_nd(x, "x", 3)
+        C = _check_nd(y, "y", 3)[2]
         Dm, P = _check_2d(models, "models")
         if grads is None:
             if workspace is None:
                 raise ValueError("a partials-only launch (grads=None) needs a workspace")
             M, Pg = int(model_row.numel()), P
-            need = M * self.grad_splits(M, int(x.shape[1]), P) * P
+            need = M * self.grad_splits(M, B, P) * P
             if workspace.numel() < need:
                 raise ValueError(f"partials-only launch needs a workspace of {need} floats")
         else:
@@ -472,10 +470,8 @@ class Engine:
         for name, t in (("model_row", model_row), ("data_row", data_row)):
             if not t.is_cuda or t.dtype != torch.int32 or t.numel() != M or not t.is_contiguous():
                 raise TypeError(f"{name} must be a contiguous int32 CUDA tensor of {M} entries")
-        Dx, B, L = (int(v) for v in x.shape)
         if tuple(y.shape[:2]) != (Dx, B) or Pg != P:
             raise ValueError("y must be [Dx, B, C] and grads [M, P]")
-        C = int(y.shape[2])
         ws_ptr, ws_n = None, 0
         if workspace is not None:
             if not workspace.is_cuda or workspace.dtype != torch.float32 or not workspace.is_contiguous():
@@ -529,7 +525,7 @@ class Engine:
         with its ring window [d-hl .. d-1, d+1 .. d+hr] (mod D); ``alphas`` [D] fp32 CUDA (one
         coefficient per device); out [D, P] must not overlap models."""
         D, P = _check_2d(models, "models")
-        if tuple(out.shape) != (D, P) or not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous():
+        if _check_nd(out, "out", what="[D, P]") != (D, P):
             raise TypeError("out must be a contiguous [D, P] fp32 CUDA tensor")
         if not alphas.is_cuda or alphas.dtype != torch.float32 or alphas.numel() != D or not alphas.is_contiguous():
             raise TypeError("alphas must be a contiguous fp32 CUDA tensor of D entries")
@@ -545,12 +541,9 @@ class Engine:
         element stride (their row pitches may differ); ``alphas`` [count] fp32 CUDA, one coefficient
         per device of the run; rows of ``out`` outside the run are left as they are. The library
         validates the run and the layout (CFAError: CFA_E_INVALID / CFA_E_UNSUPPORTED)."""
-        for name, t in (("out", out), ("models", models)):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 \
-                    or (t.shape[1] > 1 and t.stride(1) != 1):
-                raise TypeError(f"{name} must be a 2-D fp32 CUDA tensor with unit element stride")
-        rows, P = int(models.shape[0]), int(models.shape[1])
-        if tuple(out.shape) != (rows, P):
+        out_shape = _check_nd(out, "out", pitched=True)
+        rows, P = _check_nd(models, "models", pitched=True)
+        if out_shape != (rows, P):
             raise TypeError("out must have the shape of models")
         if not alphas.is_cuda or alphas.dtype != torch.float32 or alphas.numel() < max(int(count), 1) \
                 or not alphas.is_contiguous():
@@ -569,12 +562,10 @@ class Engine:
         launch; pointer tables are int64 CUDA tensors aligned with the CSR entries.
         ``reduce=(workspace, out [M, P], splits)``: the same launch also sums a partials-only
         gradient launch's [M][splits][P] workspace into ``out``."""
-        for name, t, dt in (("out_ptrs", out_ptrs, torch.int64), ("src_ptrs", src_ptrs, torch.int64),
-                            ("state_ptrs", state_ptrs, torch.int64), ("grad_ptrs", grad_ptrs, torch.int64),
-                            ("csr_ptr", csr_ptr, torch.int32), ("csr_idx", csr_idx, torch.int32),
-                            ("csr_coef", csr_coef, torch.float32)):
-            if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
-                raise TypeError(f"{name} must be a contiguous {dt} CUDA tensor")
+        _check_tables(("out_ptrs", out_ptrs, torch.int64), ("src_ptrs", src_ptrs, torch.int64),
+                      ("state_ptrs", state_ptrs, torch.int64), ("grad_ptrs", grad_ptrs, torch.int64),
+                      ("csr_ptr", csr_ptr, torch.int32), ("csr_idx", csr_idx, torch.int32),
+                      ("csr_coef", csr_coef, torch.float32))
         E = csr_idx.numel()
         if csr_ptr.numel() != D + 1 or out_ptrs.numel() != D or state_ptrs.numel() != E or grad_ptrs.numel() != E:
             raise ValueError("tables: D+1 row pointers, D outputs, one state and one gradient slot per CSR entry")
@@ -600,11 +591,9 @@ class Engine:
         fp32 first subtraction, fp64 chain with fp64 coefficients, one rounding to fp32.
         ``mode`` != 0: the compression epilogue on [cbegin, cend) of every device, counts added
         to ``kept`` (int64 CUDA tensor of D zeroed counters)."""
-        for name, t, dt in (("out_ptrs", out_ptrs, torch.int64), ("src_ptrs", src_ptrs, torch.int64),
-                            ("csr_ptr", csr_ptr, torch.int32), ("csr_idx", csr_idx, torch.int32),
-                            ("csr_coef64", csr_coef64, torch.float64)):
-            if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
-                raise TypeError(f"{name} must be a contiguous {dt} CUDA tensor")
+        _check_tables(("out_ptrs", out_ptrs, torch.int64), ("src_ptrs", src_ptrs, torch.int64),
+                      ("csr_ptr", csr_ptr, torch.int32), ("csr_idx", csr_idx, torch.int32),
+                      ("csr_coef64", csr_coef64, torch.float64))
         if csr_ptr.numel() != D + 1 or out_ptrs.numel() != D:
             raise ValueError("csr_ptr must have D+1 entries and out_ptrs D entries")
         if mode and (kept is None or not kept.is_cuda or kept.dtype != torch.int64 or kept.numel() != D):
@@ -618,11 +607,9 @@ class Engine:
                    stream=None) -> None:
         """One launch mixing D devices; tables are device tensors (int64 pointers, int32 CSR,
         fp32 coefficients). See cfa_mix_population_f32."""
-        for name, t, dt in (("out_ptrs", out_ptrs, torch.int64), ("src_ptrs", src_ptrs, torch.int64),
-                            ("csr_ptr", csr_ptr, torch.int32), ("csr_idx", csr_idx, torch.int32),
-                            ("csr_coef", csr_coef, torch.float32)):
-            if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
-                raise TypeError(f"{name} must be a contiguous {dt} CUDA tensor")
+        _check_tables(("out_ptrs", out_ptrs, torch.int64), ("src_ptrs", src_ptrs, torch.int64),
+                      ("csr_ptr", csr_ptr, torch.int32), ("csr_idx", csr_idx, torch.int32),
+                      ("csr_coef", csr_coef, torch.float32))
         if csr_ptr.numel() != D + 1 or out_ptrs.numel() != D:
             raise ValueError("csr_ptr must have D+1 entries and out_ptrs D entries")
         _lib.call("cfa_mix_population_f32", out_ptrs.data_ptr(), src_ptrs.data_ptr(),

@@ -1,5 +1,5 @@
 """The completion word of the zero-copy drop-in calls (cfa_stream_signal / cfa_wait_signal,
-consensus/_runtime._ZeroCopyPlan.complete) on the GPU: the host returns only once the mix's
+consensus/_runtime._RowPlan.finish) on the GPU: the host returns only once the mix's
 output is in pinned memory, whichever way the wait ends.
 
 - the spin path (default): back-to-back calls on changing inputs, each result read right after

@@ -1,4 +1,4 @@
-"""The completion word (consensus/_runtime._ZeroCopyPlan.complete) at multi-MB buckets, one test
+"""The completion word (consensus/_runtime._RowPlan.finish) at multi-MB buckets, one test
 per zero-copy kind: the kernels' output is written into pinned host memory from every XCD (a
 3.1M-element bucket is many chunks of tiles per XCD), and the host reads it right after the
 one-lane signal kernel of the same stream has released the word. Each call's result must equal

@@ -131,3 +131,53 @@ def test_sharded_population_exchange_gloo(world, L, h, hr):
     for p in procs:
         p.join(timeout=60)
     assert res == {r: True for r in range(world)}
+
+
+# -- the pure helpers of the host-array front end (consensus/_runtime.py; no library is loaded) ----
+_SHAPES = [(3, 3, 1, 4), (4,), (255, 6), (7,)]  # offsets 0, 36, 40, 1570, 1577
+
+
+def test_runtime_compress_range():
+    from federated_amd.consensus import _runtime as R
+    lay = R._layout_of([np.empty(s, np.float32) for s in _SHAPES])
+    assert R._compress_range(lay, None) == (0, 0, 0)
+    assert R._compress_range(lay, (2, 2)) == (2, 40, 1570)
+    assert R._compress_range(lay, (4, 3)) == (4, 1570, 1577)
+    with pytest.raises(ValueError, match="bad compression layer"):
+        R._compress_range(lay, (2, -1))  # offsets[-1], offsets[0]: begin P above end 0
+
+    class Beyond:  # a segment that ends past the bucket
+        P = 100
+        segment = staticmethod(lambda k: (96, 104))
+    with pytest.raises(ValueError, match="bad compression layer"):
+        R._compress_range(Beyond, (1, 0))
+
+
+def test_runtime_lr_split():
+    from federated_amd.consensus import _runtime as R
+    lay = R._layout_of([np.empty(s, np.float32) for s in _SHAPES])
+    assert R._lr_split(lay, (0.1, 0.1, 0.1, 0.1)) == (0.1, 0.1, 1577)  # one rate: the split is P
+    assert R._lr_split(lay, (0.1, 0.1, 0.2, 0.2)) == (0.1, 0.2, 40)
+    assert R._lr_split(lay, (0.1, 0.2, 0.2, 0.2)) == (0.1, 0.2, 36)
+    for bad in [(0.1, 0.2, 0.1, 0.2), (0.1, 0.1, 0.2, 0.3), (0.1, 0.2, 0.2, 0.1)]:
+        with pytest.raises(ValueError, match="learning rates"):
+            R._lr_split(lay, bad)
+
+
+def test_runtime_runs_and_bounds():
+    from federated_amd.consensus import _runtime as R
+    assert R._runs([]) == []
+    assert R._runs([True]) == [(0, 1, True)]
+    assert R._runs([True, True, False, True]) == [(0, 2, True), (2, 3, False), (3, 4, True)]
+    assert R._runs((5, 5, 5, 5)) == [(0, 4, 5)]
+    lay = R._layout_of([np.empty(s, np.float32) for s in _SHAPES])
+    assert R._run_bounds(lay, (True, True, False, True)) == [(0, 40, True), (40, 1570, False), (1570, 1577, True)]
+    assert R._run_bounds(lay, (1, 1, 1, 1)) == [(0, 1577, 1)]
+    # a range clipped to a run, counted from the run's first element
+    assert R._clip(40, 1570, 0, 40) == (0, 0)         # ends where the run begins
+    assert R._clip(40, 1570, 40, 1570) == (0, 1530)   # the run itself
+    assert R._clip(36, 1570, 0, 40) == (36, 40)       # across a run boundary: the part in the first run
+    assert R._clip(36, 1570, 40, 1577) == (0, 1530)   # and the part in the next
+    assert R._clip(50, 60, 40, 1577) == (10, 20)
+    assert R._clip(0, 0, 0, 40) == (0, 0)             # no compression
+    assert R._clip(36, 36, 0, 40) == (0, 0)           # an empty layer

@@ -49,7 +49,7 @@ st = mx._stream()
 out = {}
 for kind, dt in (("f32", np.float32), ("f64", np.float64)):
     plan = mx._zc_plan(kind, R._layout_of(local), N, dt)
-    sh = plan.stream_handle(st)
+    sh = plan.begin(st)
     co = plan.coeffs(al, kind == "f64")
     if kind == "f32":
         launch = lambda: plan.lib.cfa_mix_seq_f32(plan.ob, plan.hb, plan.table, co, N, plan.P, sh)

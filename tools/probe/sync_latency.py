@@ -53,7 +53,7 @@ mx = R.mixer()
 mx.mix(local, nbrs, al)
 st = mx._stream()
 plan = mx._zc_plan("f32", R._layout_of(local), 2, np.float32)
-sh = plan.stream_handle(st)
+sh = plan.begin(st)
 co = plan.coeffs(al)
 L = plan.lib
 
