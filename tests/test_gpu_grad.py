@@ -1,6 +1,10 @@
-"""(f3) HIP gradient kernels (cfa_ge_grad_cnn_f32 / cfa_ge_grad_2nn_f32) against the oracle's
-float64 gradients of the TF1 graphs (cfa_ge_2stage.py:391-433): fp32 kernels, tolerance
-1e-5 normwise per tensor (max|g - r| <= 1e-5 max|r|, the north-star fp32 bar)."""
+"""(f3) HIP gradient kernels against the oracle's float64 gradients of the TF1 graphs
+(cfa_ge_2stage.py:391-433): fp32 kernels, tolerance 1e-5 normwise per tensor (max|g - r| <=
+1e-5 max|r|, the north-star fp32 bar). Every test here reaches the kernels through the rows
+forms (cfa_ge_grad_cnn_rows_f32 / cfa_ge_grad_2nn_rows_f32: gradients_batched and
+Engine.grad_rows), at the two CFA-GE model shapes and three small CNN geometries; the plain
+entry points (cfa_ge_grad_cnn_f32 / cfa_ge_grad_2nn_f32) and the other paths of cfa_grad.hip are
+in test_gpu_grad_paths.py."""
 import numpy as np
 import pytest
 
@@ -25,7 +29,9 @@ def _check(got, models, ref_fn):
             assert normwise_close(a, r, 1e-5), (np.abs(a - r).max(), np.abs(r).max())
 
 
-@pytest.mark.parametrize("B,M", [(24, 2), (24, 5), (1, 1), (100, 3)])  # 100: chunked through LDS
+# 100: 8 batch splits of 13 samples (gradients_batched passes a workspace), each in one LDS chunk:
+# the MI355X reports 160 KiB of LDS per workgroup, which holds 33 samples of this shape
+@pytest.mark.parametrize("B,M", [(24, 2), (24, 5), (1, 1), (100, 3)])
 def test_cnn_gradients_match_oracle(gpu, B, M):
     from federated_amd.consensus import _tf1_models as T
     rng = np.random.default_rng(B * 10 + M)
@@ -48,7 +54,9 @@ def test_cnn_other_geometries(gpu, L, S, F):
     _check(got, models, lambda m: orc.tf1_cnn_grads(x, y, *m, stride=S))
 
 
-@pytest.mark.parametrize("B,M", [(24, 2), (300, 2), (3, 4)])  # 300: chunked through LDS
+# 300: 3 batch splits of 100 samples, each through LDS in chunks of 36, 36 and 28 (160 KiB of LDS
+# holds 36 samples of this shape): split and chunked in one launch
+@pytest.mark.parametrize("B,M", [(24, 2), (300, 2), (3, 4)])
 def test_2nn_gradients_match_oracle(gpu, B, M):
     from federated_amd.consensus import _tf1_models as T
     rng = np.random.default_rng(B + M)
