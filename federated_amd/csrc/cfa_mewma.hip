@@ -71,6 +71,11 @@ extern "C" int cfa_mewma_update_f32(float* W, float* const* s, const float* cons
   if (n < 0) return fail(CFA_E_INVALID, "negative fan-in %d", n);
   if (P == 0 || n == 0) return CFA_OK;
   if (!W || !s || !g) return fail(CFA_E_INVALID, "null W/s/g");
+  // every bucket of every pass before the first launch: a refused call leaves W and s as they were
+  for (int j = 0; j < n; ++j) {
+    if (!s[j] || !g[j]) return fail(CFA_E_INVALID, "null s/g bucket %d", j);
+    if (g_stride && g_stride[j] < 1) return fail(CFA_E_INVALID, "gradient stride < 1");
+  }
   hipStream_t st = (hipStream_t)stream;
   return for_each_pass(n, [&](int done, int m, bool) -> int {
     MewmaArgs a{};
@@ -85,11 +90,9 @@ extern "C" int cfa_mewma_update_f32(float* W, float* const* s, const float* cons
     a.filtered = use_filtered;
     bool vec = (addr(W) & 15) == 0;
     for (int j = 0; j < m; ++j) {
-      if (!s[done + j] || !g[done + j]) return fail(CFA_E_INVALID, "null s/g bucket %d", done + j);
       a.s[j] = s[done + j];
       a.g[j] = g[done + j];
       a.gstride[j] = g_stride ? g_stride[done + j] : 1;
-      if (a.gstride[j] < 1) return fail(CFA_E_INVALID, "gradient stride < 1");
       vec = vec && a.gstride[j] == 1 && (addr(a.s[j]) & 15) == 0 && (addr(a.g[j]) & 15) == 0;
     }
     long long begin = 0;

@@ -617,18 +617,21 @@ extern "C" int cfa_mewma_tf1_f64(double* W, double* const* s, const double* cons
     return fail(CFA_E_INVALID, "unknown dtype mask bits 0x%x", f32_mask);
   if (P == 0 || n == 0) return CFA_OK;
   if (!W) return fail(CFA_E_INVALID, "null W");
+  // every bucket of every pass before the first launch: a refused call leaves W and s as they were
+  for (int j = 0; j < n; ++j) {
+    if (!s[j] || !g[j]) return fail(CFA_E_INVALID, "null state/gradient %d", j);
+    const long long gs = g_stride ? (long long)g_stride[j] : 1;
+    if (gs < 1) return fail(CFA_E_INVALID, "gradient stride %lld < 1", gs);
+  }
   hipStream_t st = (hipStream_t)stream;
   return for_each_pass(n, [&](int done, int m, bool) -> int {
     MewmaF64Args a{};
     a.W = W;
     a.n = m;
     for (int j = 0; j < m; ++j) {
-      if (!s[done + j] || !g[done + j]) return fail(CFA_E_INVALID, "null state/gradient %d", done + j);
-      const long long gs = g_stride ? (long long)g_stride[done + j] : 1;
-      if (gs < 1) return fail(CFA_E_INVALID, "gradient stride %lld < 1", gs);
       a.s[j] = s[done + j];
       a.g[j] = g[done + j];
-      a.gstride[j] = gs;
+      a.gstride[j] = g_stride ? (long long)g_stride[done + j] : 1;
     }
     a.rho = rho;
     a.one_minus_rho = 1.0 - rho;  // Python: (1 - self.mewma)

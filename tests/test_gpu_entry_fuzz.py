@@ -210,7 +210,7 @@ def test_entry_point_fuzz(gpu, case):
         return
 
     # MEWMA (fp32 buckets: cfa_mewma_update_f32; fp64: cfa_mewma_tf1_f64, all-fp64 arrays)
-    n = max(1, min(n, 8))
+    n = max(1, n)
     rho = float(rng.choice([0.99, 0.9, 0.5]))
     lr1, lr2 = float(rng.uniform(1e-3, 0.2)), float(rng.uniform(1e-3, 0.2))
     split = int(rng.integers(0, P + 1)) if P else 0
