@@ -106,6 +106,11 @@ SIGNATURES = {
                                             _c_size_t, _c_int, _c_size_t, _c_size_t, _c_void_p, _c_void_p]),
     "cfa_mix_population_f32": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                         _c_int, _c_int, _c_size_t, _c_void_p]),
+    "cfa_mix_population_sched_f32": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                              _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_size_t, _c_void_p]),
+    "cfa_mix_population_sched_tf1_f32": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                                  _c_int, _c_int, _c_void_p, _c_int, _c_size_t, _c_int, _c_size_t,
+                                                  _c_size_t, _c_void_p, _c_void_p]),
     "cfa_ge_grad_cnn_f32": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
                                      _c_void_p, _c_void_p, _c_int, _c_void_p]),
     "cfa_ge_grad_2nn_f32": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p,

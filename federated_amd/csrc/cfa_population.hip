@@ -1,5 +1,5 @@
 // cfa_population.hip — whole-population rounds: the CSR one-launch kernel
-// (cfa_mix_population_f32) and the sliding-window passes (cfa_mix_window_f32) that load each
+// (cfa_mix_population_f32; _sched_f32 with a table per round) and the sliding-window passes (cfa_mix_window_f32) that load each
 // row of a ring window once for up to 8 consecutive devices, and the sliding ring round
 // (cfa_mix_ring_slide_f32) that reads every row of a run of ring devices once, and the CFA-GE
 // population step. Every rule's step (seq_step, lin_step, tf1_first / tf1_step, mewma_step,
@@ -22,13 +22,11 @@ namespace {
 // ------------------------------------------------------------------------------------------
 // Population round: grid.y = device, grid.x = tiles. CSR lists each device's sources.
 // ------------------------------------------------------------------------------------------
+// csr_ptr is the round's table: D + 1 row offsets into csr_idx / csr_coef.
 template <int RULE>
-__global__ __launch_bounds__(kBlock) void population_kernel(float* const* out_ptrs,
-                                                            const float* const* src_ptrs,
-                                                            const int32_t* csr_ptr,
-                                                            const int32_t* csr_idx,
-                                                            const float* csr_coef,
-                                                            long long nvec, long long P) {
+__device__ __forceinline__ void population_body(float* const* out_ptrs, const float* const* src_ptrs,
+                                                const int32_t* csr_ptr, const int32_t* csr_idx,
+                                                const float* csr_coef, long long nvec, long long P) {
   const int d = blockIdx.y;
   const int e0 = csr_ptr[d];
   const int e1 = csr_ptr[d + 1];
@@ -83,18 +81,55 @@ __global__ __launch_bounds__(kBlock) void population_kernel(float* const* out_pt
   }
 }
 
+template <int RULE>
+__global__ __launch_bounds__(kBlock) void population_kernel(float* const* out_ptrs,
+                                                            const float* const* src_ptrs,
+                                                            const int32_t* csr_ptr,
+                                                            const int32_t* csr_idx,
+                                                            const float* csr_coef,
+                                                            long long nvec, long long P) {
+  population_body<RULE>(out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, nvec, P);
+}
+
+// Topology schedule (cfa_mix_population_sched_f32 / _sched_tf1_f32): T tables of D + 1 row offsets
+// lie back to back in csr_ptr, their offsets absolute in the shared csr_idx / csr_coef, and round r
+// mixes with table sched[r mod S]. The round counter is a device word, so a captured period of
+// rounds replays with another table each time. Every workgroup of a round reads the same counter:
+// round_advance_kernel raises it after the mix, in stream order. The lookup is one chain of
+// uniform loads (round -> sched -> the table's base) ahead of the tile loop.
+struct SchedArgs {
+  const int32_t* sched;       // [S] table index of each slot
+  unsigned long long* round;  // the round counter
+  unsigned S;
+};
+
+__device__ __forceinline__ const int32_t* sched_table(const int32_t* csr_ptr, const SchedArgs& sc) {
+  const unsigned long long r = *static_cast<const unsigned long long*>(sc.round);
+  const int t = sc.sched[r % sc.S];
+  return csr_ptr + (long long)t * ((long long)gridDim.y + 1);  // grid.y = D
+}
+
+template <int RULE>
+__global__ __launch_bounds__(kBlock) void population_sched_kernel(float* const* out_ptrs,
+                                                                  const float* const* src_ptrs,
+                                                                  const int32_t* csr_ptr,
+                                                                  const int32_t* csr_idx,
+                                                                  const float* csr_coef, SchedArgs sc,
+                                                                  long long nvec, long long P) {
+  population_body<RULE>(out_ptrs, src_ptrs, sched_table(csr_ptr, sc), csr_idx, csr_coef, nvec, P);
+}
+
+__global__ void round_advance_kernel(unsigned long long* round) { *round += 1; }
+
 // TF1 population round (cfa_mix_population_tf1_f32): per device the numpy-2 chain of the TF1
 // modules (cfa.py:66-76): the first subtraction x_1 - w of two fp32 arrays is fp32, every later
 // operation fp64 with the fp64 coefficients eps * wf_j, one rounding to fp32 at the end. A TF1
 // driver assigns the returned fp64 arrays into its fp32 TF variables, so fp32 buckets mixed this
 // way follow the reference run's trajectory exactly. Same operations as cfa_mix_tf1_f32.
-__global__ __launch_bounds__(kBlock) void population_tf1_kernel(float* const* out_ptrs,
-                                                                const float* const* src_ptrs,
-                                                                const int32_t* csr_ptr,
-                                                                const int32_t* csr_idx,
-                                                                const double* csr_coef,
-                                                                long long nvec, long long P,
-                                                                CompressParams cp) {
+__device__ __forceinline__ void population_tf1_body(float* const* out_ptrs, const float* const* src_ptrs,
+                                                    const int32_t* csr_ptr, const int32_t* csr_idx,
+                                                    const double* csr_coef, long long nvec, long long P,
+                                                    const CompressParams& cp) {
   const int d = blockIdx.y;
   const int e0 = csr_ptr[d], e1 = csr_ptr[d + 1];
   float* out = out_ptrs[d];
@@ -148,6 +183,26 @@ __global__ __launch_bounds__(kBlock) void population_tf1_kernel(float* const* ou
     }
   }
   if (cp.mode) block_add_count(kept, cp.kept + d);
+}
+
+__global__ __launch_bounds__(kBlock) void population_tf1_kernel(float* const* out_ptrs,
+                                                                const float* const* src_ptrs,
+                                                                const int32_t* csr_ptr,
+                                                                const int32_t* csr_idx,
+                                                                const double* csr_coef,
+                                                                long long nvec, long long P,
+                                                                CompressParams cp) {
+  population_tf1_body(out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, nvec, P, cp);
+}
+
+__global__ __launch_bounds__(kBlock) void population_tf1_sched_kernel(float* const* out_ptrs,
+                                                                      const float* const* src_ptrs,
+                                                                      const int32_t* csr_ptr,
+                                                                      const int32_t* csr_idx,
+                                                                      const double* csr_coef, SchedArgs sc,
+                                                                      long long nvec, long long P,
+                                                                      CompressParams cp) {
+  population_tf1_body(out_ptrs, src_ptrs, sched_table(csr_ptr, sc), csr_idx, csr_coef, nvec, P, cp);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -560,11 +615,24 @@ extern "C" int cfa_mix_ring_slide_f32(float* out, size_t out_pitch, const float*
   return check_launch("ring_slide");
 }
 
-extern "C" int cfa_mix_population_tf1_f32(float* const* out_ptrs, const float* const* src_ptrs,
-                                          const int32_t* csr_ptr, const int32_t* csr_idx,
-                                          const double* csr_coef, int D, size_t P, int mode,
-                                          size_t cbegin, size_t cend, unsigned long long* kept_counts,
-                                          void* stream) {
+// A scheduled entry's own arguments, checked before anything else; sc.sched == nullptr below
+// stands for the static entry points' one table.
+static int sched_args(const int32_t* sched, int S, int T, unsigned long long* round, SchedArgs& sc) {
+  if (S <= 0 || T <= 0) return fail(CFA_E_INVALID, "schedule of %d slots over %d tables", S, T);
+  if (!sched || !round) return fail(CFA_E_INVALID, "null schedule or round counter");
+  sc = SchedArgs{sched, round, (unsigned)S};
+  return CFA_OK;
+}
+// The round is over: the next launch on the stream reads the counter one higher.
+static int advance_round(const SchedArgs& sc, hipStream_t st) {
+  round_advance_kernel<<<1, 1, 0, st>>>(sc.round);
+  return check_launch("round_advance");
+}
+
+static int population_tf1(float* const* out_ptrs, const float* const* src_ptrs, const int32_t* csr_ptr,
+                          const int32_t* csr_idx, const double* csr_coef, const SchedArgs& sc, int D,
+                          size_t P, int mode, size_t cbegin, size_t cend, unsigned long long* kept_counts,
+                          void* stream) {
   if (D < 0) return fail(CFA_E_INVALID, "negative device count");
   CompressParams cp{};
   if (int rc = compress_params(mode, cp)) return rc;
@@ -579,15 +647,42 @@ extern "C" int cfa_mix_population_tf1_f32(float* const* out_ptrs, const float* c
   if (D > 65535) return fail(CFA_E_INVALID, "D=%d exceeds grid.y limit", D);
   const long long nvec = (long long)P / 4;
   const unsigned gx = shared_grid_x((nvec + kBlock - 1) / kBlock, pop_wg_per_cu(), D);
-  population_tf1_kernel<<<dim3(gx, (unsigned)D), kBlock, 0, (hipStream_t)stream>>>(
-      out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, nvec, (long long)P, cp);
-  return check_launch("population_tf1");
+  hipStream_t st = (hipStream_t)stream;
+  if (!sc.sched) {
+    population_tf1_kernel<<<dim3(gx, (unsigned)D), kBlock, 0, st>>>(
+        out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, nvec, (long long)P, cp);
+    return check_launch("population_tf1");
+  }
+  population_tf1_sched_kernel<<<dim3(gx, (unsigned)D), kBlock, 0, st>>>(
+      out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, sc, nvec, (long long)P, cp);
+  if (int rc = check_launch("population_tf1_sched")) return rc;
+  return advance_round(sc, st);
 }
 
-extern "C" int cfa_mix_population_f32(float* const* out_ptrs, const float* const* src_ptrs,
-                                      const int32_t* csr_ptr, const int32_t* csr_idx,
-                                      const float* csr_coef, int D, int rule, size_t P,
-                                      void* stream) {
+extern "C" int cfa_mix_population_tf1_f32(float* const* out_ptrs, const float* const* src_ptrs,
+                                          const int32_t* csr_ptr, const int32_t* csr_idx,
+                                          const double* csr_coef, int D, size_t P, int mode,
+                                          size_t cbegin, size_t cend, unsigned long long* kept_counts,
+                                          void* stream) {
+  return population_tf1(out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, SchedArgs{}, D, P, mode, cbegin, cend,
+                        kept_counts, stream);
+}
+
+extern "C" int cfa_mix_population_sched_tf1_f32(float* const* out_ptrs, const float* const* src_ptrs,
+                                                const int32_t* csr_ptr, const int32_t* csr_idx,
+                                                const double* csr_coef, const int32_t* sched, int S, int T,
+                                                unsigned long long* round, int D, size_t P, int mode,
+                                                size_t cbegin, size_t cend, unsigned long long* kept_counts,
+                                                void* stream) {
+  SchedArgs sc{};
+  if (int rc = sched_args(sched, S, T, round, sc)) return rc;
+  return population_tf1(out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, sc, D, P, mode, cbegin, cend,
+                        kept_counts, stream);
+}
+
+static int population_f32(float* const* out_ptrs, const float* const* src_ptrs, const int32_t* csr_ptr,
+                          const int32_t* csr_idx, const float* csr_coef, const SchedArgs& sc, int D, int rule,
+                          size_t P, void* stream) {
   if (D < 0) return fail(CFA_E_INVALID, "negative device count");
   if (rule != CFA_RULE_SEQUENTIAL && rule != CFA_RULE_LINEAR)
     return fail(CFA_E_INVALID, "unknown rule %d", rule);
@@ -600,14 +695,40 @@ extern "C" int cfa_mix_population_f32(float* const* out_ptrs, const float* const
   // host layer); the body runs on float4, the <4-element tail in the first tile column.
   const long long nvec = (long long)P / 4;
   dim3 grid(shared_grid_x((nvec + 2LL * kBlock - 1) / (2LL * kBlock), pop_wg_per_cu(), D), (unsigned)D);
+  if (!sc.sched) {
+    if (rule == CFA_RULE_SEQUENTIAL)
+      population_kernel<CFA_RULE_SEQUENTIAL><<<grid, kBlock, 0, st>>>(out_ptrs, src_ptrs, csr_ptr,
+                                                                      csr_idx, csr_coef, nvec, (long long)P);
+    else
+      population_kernel<CFA_RULE_LINEAR><<<grid, kBlock, 0, st>>>(out_ptrs, src_ptrs, csr_ptr,
+                                                                  csr_idx, csr_coef, nvec, (long long)P);
+    return check_launch("population");
+  }
   if (rule == CFA_RULE_SEQUENTIAL)
-    population_kernel<CFA_RULE_SEQUENTIAL><<<grid, kBlock, 0, st>>>(out_ptrs, src_ptrs, csr_ptr,
-                                                                    csr_idx, csr_coef, nvec, (long long)P);
+    population_sched_kernel<CFA_RULE_SEQUENTIAL><<<grid, kBlock, 0, st>>>(out_ptrs, src_ptrs, csr_ptr, csr_idx,
+                                                                          csr_coef, sc, nvec, (long long)P);
   else
-    population_kernel<CFA_RULE_LINEAR><<<grid, kBlock, 0, st>>>(out_ptrs, src_ptrs, csr_ptr,
-                                                                csr_idx, csr_coef, nvec, (long long)P);
-  if (int rc = check_launch("population")) return rc;
-  return CFA_OK;
+    population_sched_kernel<CFA_RULE_LINEAR><<<grid, kBlock, 0, st>>>(out_ptrs, src_ptrs, csr_ptr, csr_idx,
+                                                                      csr_coef, sc, nvec, (long long)P);
+  if (int rc = check_launch("population_sched")) return rc;
+  return advance_round(sc, st);
+}
+
+extern "C" int cfa_mix_population_f32(float* const* out_ptrs, const float* const* src_ptrs,
+                                      const int32_t* csr_ptr, const int32_t* csr_idx,
+                                      const float* csr_coef, int D, int rule, size_t P,
+                                      void* stream) {
+  return population_f32(out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, SchedArgs{}, D, rule, P, stream);
+}
+
+extern "C" int cfa_mix_population_sched_f32(float* const* out_ptrs, const float* const* src_ptrs,
+                                            const int32_t* csr_ptr, const int32_t* csr_idx,
+                                            const float* csr_coef, const int32_t* sched, int S, int T,
+                                            unsigned long long* round, int D, int rule, size_t P,
+                                            void* stream) {
+  SchedArgs sc{};
+  if (int rc = sched_args(sched, S, T, round, sc)) return rc;
+  return population_f32(out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, sc, D, rule, P, stream);
 }
 
 

@@ -616,6 +616,51 @@ class Engine:
                   csr_ptr.data_ptr(), csr_idx.data_ptr(), csr_coef.data_ptr(), int(D), int(rule),
                   int(P), self.stream_handle(stream))
 
+    @staticmethod
+    def _check_schedule(csr_ptr: torch.Tensor, out_ptrs: torch.Tensor, sched: torch.Tensor, round: torch.Tensor,
+                        D: int) -> tuple:
+        """(S, T) of a topology schedule: ``csr_ptr`` holds T tables of D+1 row offsets, ``sched``
+        S table indices (int32 CUDA, checked against T by whoever uploaded them), ``round`` the
+        one-element int64 CUDA round counter."""
+        _check_tables(("sched", sched, torch.int32), ("round", round, torch.int64))
+        if round.numel() != 1:
+            raise TypeError("round must be a one-element int64 CUDA tensor")
+        T, rest = divmod(csr_ptr.numel(), D + 1)
+        if T < 1 or rest or out_ptrs.numel() != D:
+            raise ValueError("csr_ptr must hold T >= 1 tables of D+1 entries and out_ptrs D entries")
+        return sched.numel(), T
+
+    def population_sched(self, out_ptrs: torch.Tensor, src_ptrs: torch.Tensor, csr_ptr: torch.Tensor,
+                         csr_idx: torch.Tensor, csr_coef: torch.Tensor, sched: torch.Tensor, round: torch.Tensor,
+                         D: int, rule: int, P: int, stream=None) -> None:
+        """``population`` under a topology schedule (cfa_mix_population_sched_f32): mixes with
+        table ``sched[round % S]`` of the T tables in ``csr_ptr`` (absolute offsets into the
+        shared ``csr_idx`` / ``csr_coef``) and leaves ``round`` one higher, in stream order."""
+        _check_tables(("out_ptrs", out_ptrs, torch.int64), ("src_ptrs", src_ptrs, torch.int64),
+                      ("csr_ptr", csr_ptr, torch.int32), ("csr_idx", csr_idx, torch.int32),
+                      ("csr_coef", csr_coef, torch.float32))
+        S, T = self._check_schedule(csr_ptr, out_ptrs, sched, round, D)
+        _lib.call("cfa_mix_population_sched_f32", out_ptrs.data_ptr(), src_ptrs.data_ptr(), csr_ptr.data_ptr(),
+                  csr_idx.data_ptr(), csr_coef.data_ptr(), sched.data_ptr(), S, T, round.data_ptr(), int(D),
+                  int(rule), int(P), self.stream_handle(stream))
+
+    def population_sched_tf1(self, out_ptrs: torch.Tensor, src_ptrs: torch.Tensor, csr_ptr: torch.Tensor,
+                             csr_idx: torch.Tensor, csr_coef64: torch.Tensor, sched: torch.Tensor,
+                             round: torch.Tensor, D: int, P: int, stream=None, mode: int = 0, cbegin: int = 0,
+                             cend: int = 0, kept: Optional[torch.Tensor] = None) -> None:
+        """``population_tf1`` under a topology schedule (cfa_mix_population_sched_tf1_f32); the
+        schedule arguments as ``population_sched``, the rest as ``population_tf1``."""
+        _check_tables(("out_ptrs", out_ptrs, torch.int64), ("src_ptrs", src_ptrs, torch.int64),
+                      ("csr_ptr", csr_ptr, torch.int32), ("csr_idx", csr_idx, torch.int32),
+                      ("csr_coef64", csr_coef64, torch.float64))
+        S, T = self._check_schedule(csr_ptr, out_ptrs, sched, round, D)
+        if mode and (kept is None or not kept.is_cuda or kept.dtype != torch.int64 or kept.numel() != D):
+            raise TypeError("compression needs kept: an int64 CUDA tensor of D counters")
+        _lib.call("cfa_mix_population_sched_tf1_f32", out_ptrs.data_ptr(), src_ptrs.data_ptr(), csr_ptr.data_ptr(),
+                  csr_idx.data_ptr(), csr_coef64.data_ptr(), sched.data_ptr(), S, T, round.data_ptr(), int(D),
+                  int(P), int(mode), int(cbegin), int(cend), kept.data_ptr() if kept is not None else None,
+                  self.stream_handle(stream))
+
 
 _engines: dict = {}
 

@@ -84,14 +84,45 @@ def alphas_tf1_ongraphs(eps: float) -> Callable:
 
 def csr(lists: Sequence[Sequence[int]], policy: Callable, devices: Optional[int] = None, coef_dtype=np.float32):
     """(ptr, idx, coef) numpy arrays; row d = [d] + lists[d], coef = [1] + alphas."""
-    D = len(lists) if devices is None else devices
-    ptr, idx, coef = [0], [], []
-    for d, nb in enumerate(lists):
-        idx += [d] + [int(j) for j in nb]
-        coef += [1.0] + [float(a) for a in policy(nb, d, D)]
+    return schedule_csr([lists], policy, devices, coef_dtype)
+
+
+def schedule_csr(lists_per_table: Sequence[Sequence[Sequence[int]]], policy: Callable, devices: Optional[int] = None,
+                 coef_dtype=np.float32, neighbor_base: int = 0, self_coef: float = 1.0):
+    """The CSR tables of a topology schedule (``cfa_mix_population_sched_f32``), one per entry of
+    ``lists_per_table``: (ptr[T * (D+1)], idx, coef) numpy arrays. Table t is
+    ptr[t*(D+1) : (t+1)*(D+1)], its offsets absolute positions in the idx / coef all tables
+    share: ``csr(lists_per_table[t], policy)`` with ptr shifted by the entries before it.
+    Row d = [d] + [neighbor_base + j for j in its list], coef = [self_coef] + alphas.
+    ``neighbor_base=D, self_coef=0.0`` is the ``Tf1PopulationRound`` layout (the neighbours'
+    published models are rows D .. 2D-1 of its source table; the local entry's coefficient is
+    unused)."""
+    ptr, idx, coef = [], [], []
+    for lists in lists_per_table:
+        D = len(lists) if devices is None else devices
         ptr.append(len(idx))
+        for d, nb in enumerate(lists):
+            idx += [d] + [neighbor_base + int(j) for j in nb]
+            coef += [float(self_coef)] + [float(a) for a in policy(nb, d, D)]
+            ptr.append(len(idx))
     return (np.asarray(ptr, dtype=np.int32), np.asarray(idx, dtype=np.int32),
             np.asarray(coef, dtype=coef_dtype))
+
+
+def _upload_schedule(lists_per_table, policy, sched, D, dev, **layout):
+    """Device tensors of a schedule: ((ptr, idx, coef), sched [S] int32), ``sched`` checked
+    against the table count on the host (the kernel trusts it); None = every table in turn."""
+    T = len(lists_per_table)
+    if T < 1 or any(len(lists) != D for lists in lists_per_table):
+        raise ValueError(f"a schedule needs at least one table, each of {D} neighbour lists")
+    sched = list(range(T)) if sched is None else [int(t) for t in sched]
+    if not sched:
+        raise ValueError("a schedule needs at least one slot")
+    for i, t in enumerate(sched):
+        if not 0 <= t < T:
+            raise ValueError(f"sched[{i}] = {t} is outside the {T} tables")
+    tables = tuple(torch.from_numpy(a).to(dev) for a in schedule_csr(lists_per_table, policy, D, **layout))
+    return tables, torch.tensor(sched, dtype=torch.int32, device=dev)
 
 
 def window_shape(lists: Sequence[Sequence[int]], alphas: Sequence[Sequence[float]], max_side: int = 4):
@@ -127,7 +158,36 @@ def _zero_on(t: torch.Tensor, stream) -> None:
         t.zero_()
 
 
-class PopulationRound:
+class _RoundCounter:
+    """The round counter of a scheduled population: one device word that the scheduled kernels
+    read (round r mixes with table sched[r % S]) and advance, so it needs no host between rounds.
+    Each population owns its own."""
+
+    _sched = None  # (sched [S] int32, round [1] int64) device tensors under set_schedule()
+
+    def _new_schedule(self, sched: torch.Tensor) -> None:
+        self._sched = (sched, torch.zeros(1, dtype=torch.int64, device=sched.device))
+        self._graphs = None
+
+    def reset_round(self, r: int = 0) -> None:
+        """The next round is round ``r`` (it mixes with table sched[r % S]); written in the order
+        of the current stream, so rounds already enqueued there keep their tables."""
+        if self._sched is None:
+            raise RuntimeError("set_schedule() first")
+        if r < 0:
+            raise ValueError("the round index must be >= 0")
+        self._sched[1].fill_(int(r))
+
+    @property
+    def round_index(self) -> int:
+        """The number of the next round: rounds run since the last ``reset_round`` plus its
+        ``r`` (reads the device word back: synchronises)."""
+        if self._sched is None:
+            raise RuntimeError("set_schedule() first")
+        return int(self._sched[1].item())
+
+
+class PopulationRound(_RoundCounter):
     """A population of D device buckets resident in HBM, mixed in ONE launch per round."""
 
     def __init__(self, engine: Engine, models: torch.Tensor, out: Optional[torch.Tensor] = None):
@@ -160,13 +220,8 @@ class PopulationRound:
         ``compression=(mode, cbegin, cend)`` (TF1 numerics only): the cfa_ongraphs epilogue on
         every device's [cbegin, cend) segment; ``kept`` then holds each device's counter_param
         after a round."""
-        if numerics not in ("fp32", "tf1"):
-            raise ValueError("numerics must be 'fp32' or 'tf1'")
-        self._tf1 = numerics == "tf1"
-        if compression is not None and not self._tf1:
-            raise ValueError("the compression epilogue belongs to the TF1 (cfa_ongraphs) numerics")
-        self._compress = tuple(int(v) for v in compression) if compression else (0, 0, 0)
-        self.kept = torch.zeros(self.models.shape[0], dtype=torch.int64, device=self.models.device)
+        self._set_numerics(numerics, compression)
+        self._sched = None
         if use_window is None:
             use_window = self.models.shape[1] > WINDOW_MIN_P
         if self._tf1:
@@ -183,6 +238,36 @@ class PopulationRound:
                              if shape else None)
         self._graphs = None
 
+    def _set_numerics(self, numerics: str, compression) -> None:
+        if numerics not in ("fp32", "tf1"):
+            raise ValueError("numerics must be 'fp32' or 'tf1'")
+        self._tf1 = numerics == "tf1"
+        if compression is not None and not self._tf1:
+            raise ValueError("the compression epilogue belongs to the TF1 (cfa_ongraphs) numerics")
+        self._compress = tuple(int(v) for v in compression) if compression else (0, 0, 0)
+        self.kept = torch.zeros(self.models.shape[0], dtype=torch.int64, device=self.models.device)
+
+    def set_schedule(self, lists_per_table, policy, sched: Optional[Sequence[int]] = None, numerics: str = "fp32",
+                     compression: Optional[Tuple[int, int, int]] = None) -> None:
+        """A topology that changes from round to round (cfa_mobilenet.py:136-138: each epoch's
+        graph; cfa_ongraphs.py:33-52: neighbours redrawn at every call): ``lists_per_table[t]``
+        is table t's neighbour lists (``mobile(graph, t)``), and round r mixes with table
+        ``sched[r % S]`` (``sched=None``: every table in turn, S = T). All tables and the round
+        counter live on the device and the kernel looks its table up itself
+        (cfa_mix_population_sched_f32 / _sched_tf1_f32), so ``run()``, ``rounds(R, graph=False)``
+        and the graph replay of ``rounds(R)`` need no host work between rounds. Always the CSR
+        kernel, never the window or ring round. ``numerics`` / ``compression`` as
+        ``set_topology``; the counter starts at 0 (``reset_round``, ``round_index``).
+        ``set_topology`` returns the population to one fixed table.
+        Not covered: ``CfaGePopulation`` (its slot and gradient-pair tables depend on the topology
+        too) and the sharded ``RingPopulationShard`` (ring windows only)."""
+        tables, sched_t = _upload_schedule(lists_per_table, policy, sched, self.models.shape[0], self.models.device,
+                                           coef_dtype=np.float64 if numerics == "tf1" else np.float32)
+        self._set_numerics(numerics, compression)  # a refused schedule leaves the population as it was
+        self.tables = tables
+        self.window = self._ring_alphas = None
+        self._new_schedule(sched_t)
+
     def run(self, stream=None) -> torch.Tensor:
         """One round: every device's mix of ``models`` into ``out``."""
         self._launch(self.models, self.out, self.src, self.dst, stream)
@@ -190,8 +275,18 @@ class PopulationRound:
 
     def _launch(self, models, out, src, dst, stream=None) -> None:
         if self.tables is None:
-            raise RuntimeError("set_topology() first")
+            raise RuntimeError("set_topology() or set_schedule() first")
         D, P = models.shape
+        if self._sched is not None:
+            if self._tf1:
+                mode, cb, ce = self._compress
+                if mode:
+                    _zero_on(self.kept, stream)
+                self.engine.population_sched_tf1(dst, src, *self.tables, *self._sched, D, P, stream, mode, cb, ce,
+                                                 self.kept if mode else None)
+            else:
+                self.engine.population_sched(dst, src, *self.tables, *self._sched, D, RULE_SEQUENTIAL, P, stream)
+            return
         if self.window is not None:
             hl, hr, alphas = self.window
             if P % 4 == 0:  # 16-byte rows: every pass in one cfa_mix_ring_round_f32 launch
@@ -242,7 +337,7 @@ class PopulationRound:
         self._parity ^= 1
 
 
-class Tf1PopulationRound:
+class Tf1PopulationRound(_RoundCounter):
     """A device-resident population on the TF1 protocol (cfa.py:105-154, cfa_ongraphs.py): at
     epoch e every device mixes its own epoch-e model with the models its neighbours PUBLISHED at
     epoch e-1 (their pre-mix inputs of e-1, cfa.py:131-139), with the TF1 numerics (fp64 chain,
@@ -288,23 +383,36 @@ class Tf1PopulationRound:
     def previous(self) -> torch.Tensor:
         return self._bufs[(self._rot + 1) % 3]
 
+    # the source table is [current | previous]: the local entry is row d, neighbour j's published
+    # model row D + j (neighbor_base=D); fp64 coefficients, the local entry's unused
+    _LAYOUT = dict(coef_dtype=np.float64, self_coef=0.0)
+
     def set_topology(self, lists, policy, compression: Optional[Tuple[int, int, int]] = None) -> None:
         """Neighbour lists and an eps policy (``alphas_tf1_cfa`` / ``alphas_tf1_ongraphs``); the
         fp64 coefficients go to the device as they are. ``compression=(mode, cbegin, cend)``:
         the cfa_ongraphs epilogue on every device's [cbegin, cend) (its W2 segment); ``kept``
         holds each device's counter_param after a round."""
         self._compress = tuple(int(v) for v in compression) if compression else (0, 0, 0)
-        D = self.D
-        ptr, idx, coef = [0], [], []
-        for d, nb in enumerate(lists):
-            idx.append(d)
-            coef.append(0.0)
-            idx += [D + int(j) for j in nb]
-            coef += [float(a) for a in policy(nb, d, D)]
-            ptr.append(len(idx))
         dev = self._bufs[0].device
-        self._csr = (torch.tensor(ptr, dtype=torch.int32, device=dev), torch.tensor(idx, dtype=torch.int32, device=dev),
-                     torch.tensor(coef, dtype=torch.float64, device=dev))
+        self._csr = tuple(torch.from_numpy(a).to(dev)
+                          for a in schedule_csr([lists], policy, self.D, neighbor_base=self.D, **self._LAYOUT))
+        self._sched = None
+        self._graphs = None  # captured rounds hold the tables they were captured with
+
+    def set_schedule(self, lists_per_table, policy, sched: Optional[Sequence[int]] = None,
+                     compression: Optional[Tuple[int, int, int]] = None) -> None:
+        """A topology that changes from round to round: ``lists_per_table[t]`` is table t's
+        neighbour lists (``mobile(graph, t)`` for cfa_mobilenet.py:136-138) and round r mixes
+        with table ``sched[r % S]`` (``sched=None``: every table in turn). Tables and round
+        counter live on the device (cfa_mix_population_sched_tf1_f32), so ``round()`` and
+        ``rounds()``, eager or replayed from graphs, need no host work between rounds; the
+        counter starts at 0 (``reset_round``, ``round_index``). ``set_topology`` returns the
+        population to one fixed table. Not covered: ``CfaGePopulation`` and the sharded
+        ``RingPopulationShard`` (see ``PopulationRound.set_schedule``)."""
+        self._csr, sched_t = _upload_schedule(lists_per_table, policy, sched, self.D, self._bufs[0].device,
+                                              neighbor_base=self.D, **self._LAYOUT)
+        self._compress = tuple(int(v) for v in compression) if compression else (0, 0, 0)
+        self._new_schedule(sched_t)
 
     def load(self, current: torch.Tensor, previous: torch.Tensor) -> None:
         """current [D, P]: every device's epoch-e model; previous [D, P]: the models published at
@@ -314,13 +422,17 @@ class Tf1PopulationRound:
 
     def round(self, stream=None) -> None:
         if self._csr is None:
-            raise RuntimeError("set_topology() first")
+            raise RuntimeError("set_topology() or set_schedule() first")
         src, dst = self._tables[self._rot]
         mode, cb, ce = self._compress
         if mode:
             _zero_on(self.kept, stream)
-        self.engine.population_tf1(dst, src, *self._csr, self.D, self.P, stream, mode, cb, ce,
-                                   self.kept if mode else None)
+        if self._sched is not None:
+            self.engine.population_sched_tf1(dst, src, *self._csr, *self._sched, self.D, self.P, stream, mode, cb, ce,
+                                             self.kept if mode else None)
+        else:
+            self.engine.population_tf1(dst, src, *self._csr, self.D, self.P, stream, mode, cb, ce,
+                                       self.kept if mode else None)
         self._rot = (self._rot + 2) % 3  # (current, previous, out) <- (out, current, previous)
 
     def rounds(self, R: int, graph: bool = True) -> None:

@@ -556,6 +556,35 @@ CFA_API int cfa_mix_population_tf1_f32(float* const* out_ptrs, const float* cons
                                        const double* csr_coef, int D, size_t P, int mode, size_t cbegin,
                                        size_t cend, unsigned long long* kept_counts, void* stream);
 
+/* (f4) Scheduled population round: cfa_mix_population_f32 under a topology that changes from
+ * round to round (cfa_mobilenet.py:136-138 takes each epoch's neighbours from vGraph.mat,
+ * cfa_ongraphs.py:33-52 redraws them at every call) with no host work between rounds.
+ * csr_ptr holds T tables of D + 1 row offsets back to back (table t = csr_ptr + t * (D + 1)); the
+ * offsets are ABSOLUTE positions in the csr_idx / csr_coef all tables share. sched is a DEVICE
+ * array of S table indices, each in [0, T) (device memory: not checked here, the caller checks
+ * them before the upload), and round a DEVICE word, the round counter. A call mixes every device
+ * with table sched[*round mod S] and leaves *round one higher, in stream order (a one-lane launch
+ * after the mix, so every workgroup of the round reads the same value). The kernel finds its
+ * table itself: a captured sequence of calls replays any number of times, each replayed call
+ * with its own round's table. Rules, the < 4-element tail and the D <= 65535 limit as
+ * cfa_mix_population_f32. S <= 0, T <= 0 or a null sched / round: CFA_E_INVALID. D == 0 or
+ * P == 0: CFA_OK, and the counter is NOT advanced (no round was mixed). */
+CFA_API int cfa_mix_population_sched_f32(float* const* out_ptrs, const float* const* src_ptrs,
+                                         const int32_t* csr_ptr, const int32_t* csr_idx,
+                                         const float* csr_coef, const int32_t* sched, int S, int T,
+                                         unsigned long long* round, int D, int rule, size_t P,
+                                         void* stream);
+
+/* (f4) The same for cfa_mix_population_tf1_f32: its numerics, its compression epilogue and its
+ * kept_counts (zeroed by the caller before every call), with the table of the round as above
+ * (csr_coef DEVICE double, shared by all tables). D == 0 or P == 0: CFA_OK, counter not advanced. */
+CFA_API int cfa_mix_population_sched_tf1_f32(float* const* out_ptrs, const float* const* src_ptrs,
+                                             const int32_t* csr_ptr, const int32_t* csr_idx,
+                                             const double* csr_coef, const int32_t* sched, int S, int T,
+                                             unsigned long long* round, int D, size_t P, int mode,
+                                             size_t cbegin, size_t cend, unsigned long long* kept_counts,
+                                             void* stream);
+
 /* (a4 batched) CFA-GE population step: stage 1 and the gradient step of every device of a
  * device-resident population in one launch (cfa_ge_2stage.py:446-466, then :591-621). For device
  * d, CSR entries e in [csr_ptr[d], csr_ptr[d+1]): the first is its local model
