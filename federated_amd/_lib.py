@@ -34,6 +34,8 @@ RULE_LINEAR = 1
 RULE_SEQUENTIAL_DIV = 2
 RULE_ACCUMULATE = 3
 
+CLIENT_NONE, CLIENT_COPY, CLIENT_MIX = 0, 1, 2  # cfa_fedavg_population_round_f32 client rules
+
 COMPRESS_NONE = 0
 COMPRESS_SPARSE = 1
 COMPRESS_SPARSE_DPCM = 2
@@ -111,6 +113,10 @@ SIGNATURES = {
     "cfa_mix_population_sched_tf1_f32": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                                   _c_int, _c_int, _c_void_p, _c_int, _c_size_t, _c_int, _c_size_t,
                                                   _c_size_t, _c_void_p, _c_void_p]),
+    "cfa_fedavg_population_round_f32": (_c_int, [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                                 _c_void_p, ctypes.c_float, _c_void_p, _c_int, _c_int, _c_void_p,
+                                                 _c_void_p, _c_int, ctypes.c_float, ctypes.c_float, ctypes.c_double,
+                                                 _c_int, _c_size_t, _c_void_p]),
     "cfa_ge_grad_cnn_f32": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
                                      _c_void_p, _c_void_p, _c_int, _c_void_p]),
     "cfa_ge_grad_2nn_f32": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p,

@@ -662,6 +662,41 @@ class Engine:
                   self.stream_handle(stream))
 
 
+    def fedavg_round(self, models: torch.Tensor, params: torch.Tensor, act_ptr: torch.Tensor, act_idx: torch.Tensor,
+                     act_div: torch.Tensor, act_rdiv: torch.Tensor, update_factor: float, sched: torch.Tensor,
+                     round: torch.Tensor, ended: Optional[torch.Tensor] = None, client: int = _lib.CLIENT_COPY,
+                     client_factor: float = 1.0, client_divisor: float = 1.0, stream=None) -> None:
+        """cfa_fedavg_population_round_f32: one FedAvg parameter-server round on ``models`` [D, P]
+        (fp32 CUDA, unit element stride, any row pitch) and the global model ``params`` [P], both
+        in place. The round's active list is list ``sched[round % S]`` of the T lists in
+        ``act_ptr`` [T + 1] / ``act_idx`` (int32 CUDA, ``topology.active_schedule``), with its
+        divisor ``act_div`` [T] fp32 and reciprocal ``act_rdiv`` [T] fp64; ``round`` is left one
+        higher in stream order. ``ended`` [D] int32 CUDA or None: the training_end flags.
+        ``client``: _lib.CLIENT_NONE / CLIENT_COPY / CLIENT_MIX (w + client_factor * (g - w) /
+        client_divisor). The library validates alignment and pitch (CFAError)."""
+        D, P = _check_nd(models, "models", pitched=True)
+        _check_bucket(params, "params", P)
+        _check_tables(("act_ptr", act_ptr, torch.int32), ("act_idx", act_idx, torch.int32),
+                      ("act_div", act_div, torch.float32), ("act_rdiv", act_rdiv, torch.float64),
+                      ("sched", sched, torch.int32), ("round", round, torch.int64))
+        if round.numel() != 1:
+            raise TypeError("round must be a one-element int64 CUDA tensor")
+        T = act_ptr.numel() - 1
+        if T < 1 or act_div.numel() != T or act_rdiv.numel() != T or act_idx.numel() < 1:
+            raise ValueError("act_ptr must hold T + 1 >= 2 offsets, act_div and act_rdiv T entries each, and "
+                             "act_idx at least one entry")
+        if ended is not None:
+            _check_tables(("ended", ended, torch.int32))
+            if ended.numel() != D:
+                raise ValueError("ended must hold one int32 flag per device")
+        cd = float(np.float32(client_divisor))
+        _lib.call("cfa_fedavg_population_round_f32", models.data_ptr(), int(models.stride(0)) if D > 1 else P,
+                  params.data_ptr(), act_ptr.data_ptr(), act_idx.data_ptr(), act_div.data_ptr(), act_rdiv.data_ptr(),
+                  float(update_factor), sched.data_ptr(), sched.numel(), T, round.data_ptr(),
+                  ended.data_ptr() if ended is not None else None, int(client), float(client_factor), cd,
+                  1.0 / cd if cd else 0.0, D, P, self.stream_handle(stream))
+
+
 _engines: dict = {}
 
 

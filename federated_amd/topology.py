@@ -109,18 +109,52 @@ def schedule_csr(lists_per_table: Sequence[Sequence[Sequence[int]]], policy: Cal
             np.asarray(coef, dtype=coef_dtype))
 
 
-def _upload_schedule(lists_per_table, policy, sched, D, dev, **layout):
-    """Device tensors of a schedule: ((ptr, idx, coef), sched [S] int32), ``sched`` checked
-    against the table count on the host (the kernel trusts it); None = every table in turn."""
-    T = len(lists_per_table)
-    if T < 1 or any(len(lists) != D for lists in lists_per_table):
-        raise ValueError(f"a schedule needs at least one table, each of {D} neighbour lists")
+def active_schedule(lists_per_table, devices: int):
+    """The active tables of a FedAvg parameter-server schedule
+    (``cfa_fedavg_population_round_f32``): (act_ptr[T + 1] int32, act_idx int32, act_div[T] fp32,
+    act_rdiv[T] fp64) numpy arrays. ``lists_per_table`` is the reference's ``indexes_tx`` as an
+    [A, E] integer array (column e is table e: parameter_server_v2.py:88, ``active_devices =
+    self.indexes_tx[:, epoch]``), or a list of ragged lists; table t's device ids, in fold order
+    and with duplicates kept, are act_idx[act_ptr[t] : act_ptr[t + 1]] (absolute offsets, as
+    ``schedule_csr``). act_div[t] is the list's length C as fp32 and act_rdiv[t] the fp64
+    reciprocal 1.0 / act_div[t] the kernel divides with; an empty list takes the divisor 1, which
+    is never used. Ids outside [0, devices) are refused."""
+    if isinstance(lists_per_table, np.ndarray):
+        if lists_per_table.ndim != 2 or lists_per_table.dtype.kind not in "iu":
+            raise ValueError("an indexes_tx array must be a 2-D [A, E] integer array")
+        lists_per_table = [lists_per_table[:, e].tolist() for e in range(lists_per_table.shape[1])]
+    ptr, idx = [0], []
+    for t, ids in enumerate(lists_per_table):
+        for k in ids:
+            if int(k) != k or not 0 <= int(k) < devices:
+                raise ValueError(f"table {t}: device id {k} is outside [0, {devices})")
+            idx.append(int(k))
+        ptr.append(len(idx))
+    if len(idx) >= 2 ** 31:
+        raise ValueError("the active lists hold more than 2^31 - 1 entries")
+    div = np.asarray([max(b - a, 1) for a, b in zip(ptr, ptr[1:])], dtype=np.float32)
+    return (np.asarray(ptr, dtype=np.int32), np.asarray(idx, dtype=np.int32), div, 1.0 / div.astype(np.float64))
+
+
+def _check_sched(sched, T: int) -> List[int]:
+    """``sched`` as a list of table indices checked against the table count on the host (the
+    kernels trust it); None = every table in turn."""
     sched = list(range(T)) if sched is None else [int(t) for t in sched]
     if not sched:
         raise ValueError("a schedule needs at least one slot")
     for i, t in enumerate(sched):
         if not 0 <= t < T:
             raise ValueError(f"sched[{i}] = {t} is outside the {T} tables")
+    return sched
+
+
+def _upload_schedule(lists_per_table, policy, sched, D, dev, **layout):
+    """Device tensors of a schedule: ((ptr, idx, coef), sched [S] int32), ``sched`` checked
+    against the table count on the host (the kernel trusts it); None = every table in turn."""
+    T = len(lists_per_table)
+    if T < 1 or any(len(lists) != D for lists in lists_per_table):
+        raise ValueError(f"a schedule needs at least one table, each of {D} neighbour lists")
+    sched = _check_sched(sched, T)
     tables = tuple(torch.from_numpy(a).to(dev) for a in schedule_csr(lists_per_table, policy, D, **layout))
     return tables, torch.tensor(sched, dtype=torch.int32, device=dev)
 

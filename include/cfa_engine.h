@@ -135,6 +135,13 @@ enum {
   CFA_COMPRESS_SPARSE_HI = 4        /* |y| < 1e-2 -> sign(y) * 1e-3                        :261-271 */
 };
 
+/* Client rules of the FedAvg population round (cfa_fedavg_population_round_f32). */
+enum {
+  CFA_CLIENT_NONE = 0, /* only the global model is written */
+  CFA_CLIENT_COPY = 1, /* every device takes the global model as it is */
+  CFA_CLIENT_MIX = 2   /* every device mixes it in: w <- w + (u_c * (g - w)) / d_c */
+};
+
 CFA_API int cfa_version(void);
 CFA_API const char* cfa_last_error(void);
 
@@ -584,6 +591,48 @@ CFA_API int cfa_mix_population_sched_tf1_f32(float* const* out_ptrs, const float
                                              unsigned long long* round, int D, size_t P, int mode,
                                              size_t cbegin, size_t cend, unsigned long long* kept_counts,
                                              void* stream);
+
+/* (f1 batched) FedAvg parameter-server round on a device-resident population, one launch per
+ * round: the server's fold of the round's active devices into the global model, then every
+ * device's take of the published model, with no host work between rounds.
+ *   models  [D, pitch] fp32 rows (DEVICE), row d = device d's model, updated in place by the client
+ *           rule. Rows start 16-byte aligned (base aligned, pitch a multiple of 4 elements);
+ *           P <= pitch may be any size: the last P mod 4 elements take a scalar tail in the same
+ *           launch. Columns P .. pitch-1 are never touched.
+ *   params  [P] fp32 (DEVICE, 16-byte aligned), the global model, updated in place.
+ *   act_ptr [T + 1], act_idx: T active lists back to back (DEVICE); list t is act_idx[act_ptr[t] ..
+ *           act_ptr[t + 1]), device ids in fold order, duplicates allowed (the reference folds a
+ *           list: parameter_server_v2.py:88, active_devices = indexes_tx[:, epoch]). The ids are
+ *           device memory: not checked here, the caller checks them before the upload.
+ *   act_div [T] float C of each list and act_rdiv [T] double RN_64(1 / C) (DEVICE), built by the
+ *           caller as 1.0 / (double)act_div[t]: the kernel forms no reciprocal itself.
+ *   sched [S], round: as cfa_mix_population_sched_f32. The call uses list sched[*round mod S] and
+ *           leaves *round one higher, in stream order.
+ *   ended   [D] int32 flags (DEVICE), or NULL: device d reported training_end.
+ * Server (parameter_server_v2.py:146-161, parameter_server.py:154, PS_server.py:130-133): for the
+ * C entries k of the round's list in order, p <- p + (u * (x_k - p)) / C, every operation rounded
+ * to fp32 as numpy does (the CFA_RULE_SEQUENTIAL_DIV step, identical to cfa_mix_seq_div_f32 bit for
+ * bit, exact subnormal ties included). If any entry of the list is flagged in `ended`, the server
+ * instead takes the transfer-learning step p <- p + u * (x_e - p) on the FIRST flagged entry in
+ * list order, with no division, and folds nothing else (:150-157). An empty list leaves params
+ * unchanged; the client rule still runs.
+ * Client: CFA_CLIENT_NONE writes params only; CFA_CLIENT_COPY makes every row the new params
+ * (federated_learning_keras_PS_MNIST.py:307-309); CFA_CLIENT_MIX gives every row
+ * w <- w + (u_c * (g - w)) / d_c with g the new params and rd_c = RN_64(1 / d_c)
+ * (learner_consensus.py:151-152; d_c = 1 divides exactly: a plain w + u_c * (g - w) client).
+ * Rows of devices that were not active are updated too. Each lane owns its columns for the whole
+ * round (it reads and writes a given element of params and of every row itself), so the update is
+ * in place with no second stack.
+ * CFA_E_INVALID: a null table, S <= 0 or T <= 0, D < 0, pitch < P, an unknown client rule,
+ * d_c == 0 under CFA_CLIENT_MIX. CFA_E_UNSUPPORTED: a base or pitch that is not 16-byte aligned.
+ * P == 0: CFA_OK, and the counter is NOT advanced. */
+CFA_API int cfa_fedavg_population_round_f32(float* models, size_t pitch, float* params,
+                                            const int32_t* act_ptr, const int32_t* act_idx,
+                                            const float* act_div, const double* act_rdiv, float u,
+                                            const int32_t* sched, int S, int T,
+                                            unsigned long long* round, const int32_t* ended,
+                                            int client, float u_c, float d_c, double rd_c, int D,
+                                            size_t P, void* stream);
 
 /* (a4 batched) CFA-GE population step: stage 1 and the gradient step of every device of a
  * device-resident population in one launch (cfa_ge_2stage.py:446-466, then :591-621). For device
