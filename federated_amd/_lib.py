@@ -35,6 +35,7 @@ RULE_SEQUENTIAL_DIV = 2
 RULE_ACCUMULATE = 3
 
 CLIENT_NONE, CLIENT_COPY, CLIENT_MIX = 0, 1, 2  # cfa_fedavg_population_round_f32 client rules
+ENDED_COPY, ENDED_TRUNCATE, ENDED_TRUNCATE_EPS = 0, 1, 2  # cfa_mix_population_ended_f32 rules
 
 COMPRESS_NONE = 0
 COMPRESS_SPARSE = 1
@@ -113,6 +114,9 @@ SIGNATURES = {
     "cfa_mix_population_sched_tf1_f32": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                                   _c_int, _c_int, _c_void_p, _c_int, _c_size_t, _c_int, _c_size_t,
                                                   _c_size_t, _c_void_p, _c_void_p]),
+    "cfa_mix_population_ended_f32": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                              _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int,
+                                              _c_int, _c_size_t, _c_void_p]),
     "cfa_fedavg_population_round_f32": (_c_int, [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                                  _c_void_p, ctypes.c_float, _c_void_p, _c_int, _c_int, _c_void_p,
                                                  _c_void_p, _c_int, ctypes.c_float, ctypes.c_float, ctypes.c_double,

@@ -1,5 +1,6 @@
 // cfa_population.hip — whole-population rounds: the CSR one-launch kernel
-// (cfa_mix_population_f32; _sched_f32 with a table per round) and the sliding-window passes (cfa_mix_window_f32) that load each
+// (cfa_mix_population_f32; _sched_f32 with a table per round; _ended_f32 with the training_end
+// rule on device-resident flags) and the sliding-window passes (cfa_mix_window_f32) that load each
 // row of a ring window once for up to 8 consecutive devices, and the sliding ring round
 // (cfa_mix_ring_slide_f32) that reads every row of a run of ring devices once, the FedAvg
 // parameter-server round (cfa_fedavg_population_round_f32), and the CFA-GE population step. Every
@@ -24,15 +25,14 @@ namespace {
 // ------------------------------------------------------------------------------------------
 // Population round: grid.y = device, grid.x = tiles. CSR lists each device's sources.
 // ------------------------------------------------------------------------------------------
-// csr_ptr is the round's table: D + 1 row offsets into csr_idx / csr_coef.
+// The fold of CSR entries [e0, e1) into `out` by the workgroups of one device (blockIdx.x over
+// the tiles): entry e0 is the row the fold starts from, every later entry e one step with
+// csr_coef[e], or with `eps` for all of them when use_eps (the training_end round's recomputed
+// coefficient). e1 == e0 + 1 loads and stores row e0 with no arithmetic in between: a bit copy.
 template <int RULE>
-__device__ __forceinline__ void population_body(float* const* out_ptrs, const float* const* src_ptrs,
-                                                const int32_t* csr_ptr, const int32_t* csr_idx,
-                                                const float* csr_coef, long long nvec, long long P) {
-  const int d = blockIdx.y;
-  const int e0 = csr_ptr[d];
-  const int e1 = csr_ptr[d + 1];
-  float* out = out_ptrs[d];
+__device__ __forceinline__ void population_fold(float* out, const float* const* src_ptrs, const int32_t* csr_idx,
+                                                const float* csr_coef, int e0, int e1, bool use_eps, float eps,
+                                                long long nvec, long long P) {
   constexpr int U = 2;
   constexpr long long kTile = (long long)kBlock * U;
   for (long long t = blockIdx.x; t * kTile < nvec; t += gridDim.x) {
@@ -53,7 +53,7 @@ __device__ __forceinline__ void population_body(float* const* out_ptrs, const fl
     }
     for (int e = e0 + 1; e < e1; ++e) {
       const float* s = src_ptrs[csr_idx[e]];
-      const float c = csr_coef[e];
+      const float c = use_eps ? eps : csr_coef[e];
       f4 x[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) x[u] = ok[u] ? ld4<true>(s, idx[u]) : f4{0.f, 0.f, 0.f, 0.f};
@@ -75,12 +75,21 @@ __device__ __forceinline__ void population_body(float* const* out_ptrs, const fl
     if constexpr (RULE == CFA_RULE_LINEAR) w = csr_coef[e0] * w;
     for (int e = e0 + 1; e < e1; ++e) {
       const float x = src_ptrs[csr_idx[e]][i];
-      const float c = csr_coef[e];
+      const float c = use_eps ? eps : csr_coef[e];
       if constexpr (RULE == CFA_RULE_SEQUENTIAL) w = seq_step(w, x, c);
       else w = lin_step(w, x, c);
     }
     out[i] = w;
   }
+}
+
+// csr_ptr is the round's table: D + 1 row offsets into csr_idx / csr_coef.
+template <int RULE>
+__device__ __forceinline__ void population_body(float* const* out_ptrs, const float* const* src_ptrs,
+                                                const int32_t* csr_ptr, const int32_t* csr_idx,
+                                                const float* csr_coef, long long nvec, long long P) {
+  const int d = blockIdx.y;
+  population_fold<RULE>(out_ptrs[d], src_ptrs, csr_idx, csr_coef, csr_ptr[d], csr_ptr[d + 1], false, 0.f, nvec, P);
 }
 
 template <int RULE>
@@ -122,6 +131,69 @@ __global__ __launch_bounds__(kBlock) void population_sched_kernel(float* const* 
 }
 
 __global__ void round_advance_kernel(unsigned long long* round) { *round += 1; }
+
+// training_end round (cfa_mix_population_ended_f32): the population round with the TF2 protocol's
+// training_end rule (consensus_v3.py:139-152, :233; consensus_v4.py:191-210, :234-248). A device
+// that has ended keeps its row; any other collects its list up to and including the first
+// neighbour flagged in `ended` and, by ended_rule, takes that neighbour's row as it is (COPY),
+// folds the collected prefix with the table's coefficients (TRUNCATE), or folds it with
+// 1 / (prefix length + 1) (TRUNCATE_EPS, also with no flagged neighbour: the whole list). Each
+// case is a range of CSR entries handed to population_fold. Every workgroup of a device reaches
+// the same range from `ended` alone: ended_next and saw are written by this launch (one lane of
+// the device's first workgroup) and never read by it.
+struct EndedArgs {
+  const int32_t* ended;  // [D] the round's input flags
+  int32_t* ended_next;   // [D] ended | saw, or null
+  int32_t* saw;          // [D] a flagged neighbour was collected, or null
+  int rule;
+};
+
+// The first entry of [b, e) whose device is flagged, e when there is none: the workgroup's lanes
+// take one entry each per pass and keep the smallest flagged position (as fedavg_round_lookup).
+// Called by every lane of the workgroup (it synchronises).
+__device__ __forceinline__ int first_ended(const int32_t* ended, const int32_t* csr_idx, int b, int e) {
+  __shared__ int first;
+  if (threadIdx.x == 0) first = e;
+  __syncthreads();
+  for (int k = b + (int)threadIdx.x; k < e; k += kBlock)
+    if (ended[csr_idx[k]]) {
+      atomicMin(&first, k);
+      break;
+    }
+  __syncthreads();
+  return __builtin_amdgcn_readfirstlane(first);
+}
+
+template <bool SCHED>
+__global__ __launch_bounds__(kBlock) void population_ended_kernel(float* const* out_ptrs,
+                                                                  const float* const* src_ptrs,
+                                                                  const int32_t* csr_ptr,
+                                                                  const int32_t* csr_idx,
+                                                                  const float* csr_coef, SchedArgs sc,
+                                                                  EndedArgs ea, long long nvec, long long P) {
+  const int32_t* ptr = csr_ptr;
+  if constexpr (SCHED) ptr = sched_table(csr_ptr, sc);
+  const int d = blockIdx.y;
+  int e0 = ptr[d], e1 = ptr[d + 1];
+  const bool self = ea.ended[d] != 0;  // uniform over the device's workgroups, as everything below
+  int f = e1;
+  if (!self) f = first_ended(ea.ended, csr_idx, e0 + 1, e1);
+  const bool found = f < e1;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (ea.saw) ea.saw[d] = found;
+    if (ea.ended_next) ea.ended_next[d] = self || found;
+  }
+  if (self) {
+    e1 = e0 + 1;  // the device has left its loop: its own row
+  } else if (found) {
+    if (ea.rule == CFA_ENDED_COPY) e0 = f;  // that neighbour's row and nothing else
+    e1 = f + 1;
+  }
+  // numpy's Python float 1 / (len + 1) on fp32 arrays: one fp64 division, one rounding to fp32
+  const bool use_eps = !self && ea.rule == CFA_ENDED_TRUNCATE_EPS;
+  const float eps = use_eps ? (float)(1.0 / (double)(e1 - e0)) : 0.f;
+  population_fold<CFA_RULE_SEQUENTIAL>(out_ptrs[d], src_ptrs, csr_idx, csr_coef, e0, e1, use_eps, eps, nvec, P);
+}
 
 // TF1 population round (cfa_mix_population_tf1_f32): per device the numpy-2 chain of the TF1
 // modules (cfa.py:66-76): the first subtraction x_1 - w of two fp32 arrays is fp32, every later
@@ -731,6 +803,46 @@ extern "C" int cfa_mix_population_sched_f32(float* const* out_ptrs, const float*
   SchedArgs sc{};
   if (int rc = sched_args(sched, S, T, round, sc)) return rc;
   return population_f32(out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, sc, D, rule, P, stream);
+}
+
+// [a, a + n) and [b, b + n) share an element.
+static bool flags_overlap(const int32_t* a, const int32_t* b, int n) {
+  return b && addr(a) < addr(b + n) && addr(b) < addr(a + n);
+}
+
+extern "C" int cfa_mix_population_ended_f32(float* const* out_ptrs, const float* const* src_ptrs,
+                                            const int32_t* csr_ptr, const int32_t* csr_idx,
+                                            const float* csr_coef, const int32_t* sched, int S, int T,
+                                            unsigned long long* round, const int32_t* ended,
+                                            int32_t* ended_next, int32_t* saw, int ended_rule, int D,
+                                            size_t P, void* stream) {
+  SchedArgs sc{};
+  if (sched || round)
+    if (int rc = sched_args(sched, S, T, round, sc)) return rc;
+  if (D < 0) return fail(CFA_E_INVALID, "negative device count");
+  if (ended_rule != CFA_ENDED_COPY && ended_rule != CFA_ENDED_TRUNCATE && ended_rule != CFA_ENDED_TRUNCATE_EPS)
+    return fail(CFA_E_INVALID, "unknown ended rule %d", ended_rule);
+  if (!ended) return fail(CFA_E_INVALID, "null ended flags");
+  // every workgroup of the round reads `ended` while one lane per device writes the other two
+  if (flags_overlap(ended, ended_next, D > 0 ? D : 1) || flags_overlap(ended, saw, D > 0 ? D : 1))
+    return fail(CFA_E_INVALID, "ended_next or saw aliases ended");
+  if (D == 0 || P == 0) return CFA_OK;
+  if (!out_ptrs || !src_ptrs || !csr_ptr || !csr_idx || !csr_coef)
+    return fail(CFA_E_INVALID, "null population table");
+  if (D > 65535) return fail(CFA_E_INVALID, "D=%d exceeds grid.y limit", D);
+  hipStream_t st = (hipStream_t)stream;
+  const EndedArgs ea{ended, ended_next, saw, ended_rule};
+  const long long nvec = (long long)P / 4;  // buckets 16-byte aligned, as cfa_mix_population_f32
+  dim3 grid(shared_grid_x((nvec + 2LL * kBlock - 1) / (2LL * kBlock), pop_wg_per_cu(), D), (unsigned)D);
+  if (!sc.sched) {
+    population_ended_kernel<false><<<grid, kBlock, 0, st>>>(out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, sc, ea,
+                                                            nvec, (long long)P);
+    return check_launch("population_ended");
+  }
+  population_ended_kernel<true><<<grid, kBlock, 0, st>>>(out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, sc, ea,
+                                                         nvec, (long long)P);
+  if (int rc = check_launch("population_ended_sched")) return rc;
+  return advance_round(sc, st);
 }
 
 // ------------------------------------------------------------------------------------------

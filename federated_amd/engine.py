@@ -661,6 +661,39 @@ class Engine:
                   int(P), int(mode), int(cbegin), int(cend), kept.data_ptr() if kept is not None else None,
                   self.stream_handle(stream))
 
+    def population_ended(self, out_ptrs: torch.Tensor, src_ptrs: torch.Tensor, csr_ptr: torch.Tensor,
+                         csr_idx: torch.Tensor, csr_coef: torch.Tensor, ended: torch.Tensor,
+                         ended_next: Optional[torch.Tensor], saw: Optional[torch.Tensor], ended_rule: int, D: int,
+                         P: int, sched: Optional[torch.Tensor] = None, round: Optional[torch.Tensor] = None,
+                         stream=None) -> None:
+        """``population`` (sequential rule) with the training_end rule on device-resident flags
+        (cfa_mix_population_ended_f32). ``ended`` [D] int32 CUDA: the round's input flags;
+        ``ended_next`` (``ended | saw``) and ``saw`` (a flagged neighbour was collected) are int32
+        CUDA tensors of D entries or None, written by the launch. ``ended_rule``:
+        _lib.ENDED_COPY / ENDED_TRUNCATE / ENDED_TRUNCATE_EPS. With ``sched`` and ``round`` the
+        tables and the counter are those of ``population_sched``; with neither, one table."""
+        _check_tables(("out_ptrs", out_ptrs, torch.int64), ("src_ptrs", src_ptrs, torch.int64),
+                      ("csr_ptr", csr_ptr, torch.int32), ("csr_idx", csr_idx, torch.int32),
+                      ("csr_coef", csr_coef, torch.float32), ("ended", ended, torch.int32))
+        for name, t in (("ended", ended), ("ended_next", ended_next), ("saw", saw)):
+            if t is not None:
+                _check_tables((name, t, torch.int32))
+                if t.numel() != D:
+                    raise ValueError(f"{name} must hold one int32 flag per device")
+        if (sched is None) != (round is None):
+            raise ValueError("sched and round are given together or not at all")
+        if sched is None:
+            if csr_ptr.numel() != D + 1 or out_ptrs.numel() != D:
+                raise ValueError("csr_ptr must have D+1 entries and out_ptrs D entries")
+            S = T = 0
+        else:
+            S, T = self._check_schedule(csr_ptr, out_ptrs, sched, round, D)
+        _lib.call("cfa_mix_population_ended_f32", out_ptrs.data_ptr(), src_ptrs.data_ptr(), csr_ptr.data_ptr(),
+                  csr_idx.data_ptr(), csr_coef.data_ptr(), sched.data_ptr() if sched is not None else None, S, T,
+                  round.data_ptr() if round is not None else None, ended.data_ptr(),
+                  ended_next.data_ptr() if ended_next is not None else None,
+                  saw.data_ptr() if saw is not None else None, int(ended_rule), int(D), int(P),
+                  self.stream_handle(stream))
 
     def fedavg_round(self, models: torch.Tensor, params: torch.Tensor, act_ptr: torch.Tensor, act_idx: torch.Tensor,
                      act_div: torch.Tensor, act_rdiv: torch.Tensor, update_factor: float, sched: torch.Tensor,

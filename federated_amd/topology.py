@@ -19,6 +19,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import _lib
 from .consensus import _tf1, _tf2
 from ._graphs import RoundGraphs
 from .engine import Engine
@@ -221,8 +222,30 @@ class _RoundCounter:
         return int(self._sched[1].item())
 
 
+_ENDED_RULES = {"copy": _lib.ENDED_COPY, "truncate": _lib.ENDED_TRUNCATE, "truncate_eps": _lib.ENDED_TRUNCATE_EPS}
+
+
+def ended_rule_code(rule: Optional[str]) -> Optional[int]:
+    """The library's constant of a ``set_ended_rule`` rule name; None stays None (the rule off)."""
+    if rule is not None and rule not in _ENDED_RULES:
+        raise ValueError("rule must be None, 'copy', 'truncate' or 'truncate_eps'")
+    return None if rule is None else _ENDED_RULES[rule]
+
+
+def ended_flags(ids, devices: int) -> np.ndarray:
+    """int32 [devices] flags, 1 for every id in ``ids``; an id outside [0, devices) is refused."""
+    flags = np.zeros(devices, dtype=np.int32)
+    for k in ids:
+        if int(k) != k or not 0 <= int(k) < devices:
+            raise ValueError(f"device id {k} is outside [0, {devices})")
+        flags[int(k)] = 1
+    return flags
+
+
 class PopulationRound(_RoundCounter):
     """A population of D device buckets resident in HBM, mixed in ONE launch per round."""
+
+    _ended_rule = None  # (library constant, propagate) under set_ended_rule()
 
     def __init__(self, engine: Engine, models: torch.Tensor, out: Optional[torch.Tensor] = None):
         if models.dim() != 2 or models.dtype != torch.float32 or not models.is_cuda:
@@ -239,6 +262,65 @@ class PopulationRound(_RoundCounter):
         self._graphs: Optional[RoundGraphs] = None  # captured rounds, rebuilt per topology
         self._parity = 0
         self._tf1 = False
+        # rows 0 / 1: the ended flags, double-buffered as models / out; row 2: saw_ended
+        self._flags = torch.zeros(3, D, dtype=torch.int32, device=dev)
+
+    def set_ended_rule(self, rule: Optional[str], propagate: bool = False) -> None:
+        """The TF2 protocol's ``training_end`` rule on the device, for the last rounds of a CFA
+        run. A device flagged in ``ended`` has left its loop and keeps its model
+        (federated_learning_keras_consensus_FL_threads_MNIST.py:501-546). Every other device
+        collects its neighbours in list order, stops after the first flagged one
+        (consensus_v3.py:139-141; consensus_v4.py:191-193, :234-236) and, by ``rule``,
+
+        - "copy": takes that neighbour's model as it is, bit for bit (federated weights,
+          consensus_v3.py:147-152, consensus_v4.py:205-210);
+        - "truncate": mixes the collected prefix with the topology's coefficients (federated
+          gradients of v4: the caller's eps, consensus_v4.py:248);
+        - "truncate_eps": mixes it with eps = 1 / (prefix length + 1), and a device without a
+          flagged neighbour its whole list with 1 / (n + 1), whatever the policy gave
+          (federated gradients of v3, consensus_v3.py:233).
+
+        With "copy" and "truncate" a device without a flagged neighbour mixes as with the rule
+        off, bit for bit. ``saw_ended`` holds every device's
+        ``getTrainingStatusFromNeightbor()`` of the last round. ``None`` (the default) turns the
+        rule off: today's rounds on today's kernels. With a rule on a round is always one
+        cfa_mix_population_ended_f32 launch on the CSR tables, never the window or ring round,
+        under ``set_topology`` and ``set_schedule`` alike (the setting survives both), and
+        ``run()``, ``rounds(R, graph=False)`` and the replay of ``rounds(R)`` need no host work
+        between rounds. ``numerics="tf1"`` has no such rule: ValueError, here or there.
+
+        ``propagate=False``: the flags change only through ``set_ended``. ``propagate=True``:
+        ``ended`` after a round is ``ended | saw_ended``, every device of round r reading round
+        r - 1's flags. That is the driver's chain of :423-425 (a device that saw training_end
+        stops learning) and :501-509 (it then validates the model it copied and ends), taken for
+        granted: a simulation convenience for a population whose devices copy an already solved
+        model bit for bit, not something the reference's consensus modules do themselves. After
+        ``run()`` and after ``rounds(R)`` for any R, ``ended`` holds the flags after the last
+        round.
+
+        Not covered: ``Tf1PopulationRound``, ``CfaGePopulation`` and the sharded populations."""
+        code = ended_rule_code(rule)
+        if code is not None and self._tf1:
+            raise ValueError("the training_end rule belongs to the TF2 numerics, not numerics='tf1'")
+        self._ended_rule = None if code is None else (code, bool(propagate))
+        self._graphs = None  # captured rounds hold the kernels they were captured with
+
+    @property
+    def ended(self) -> torch.Tensor:
+        """The current ``training_end`` flags: int32 [D] on the device, all zero at the start."""
+        return self._flags[0]
+
+    @property
+    def saw_ended(self) -> torch.Tensor:
+        """int32 [D]: 1 where the device collected a flagged neighbour in the last round with a
+        rule on (its ``getTrainingStatusFromNeightbor()``)."""
+        return self._flags[2]
+
+    def set_ended(self, ids) -> None:
+        """The devices that reported ``training_end`` (all others are cleared). Written in the
+        order of the current stream: rounds already enqueued or replayed there see the old flags,
+        later ones the new."""
+        self._flags[0].copy_(torch.from_numpy(ended_flags(ids, self.models.shape[0])), non_blocking=False)
 
     def set_topology(self, lists, policy, use_window: Optional[bool] = None, numerics: str = "fp32",
                      compression: Optional[Tuple[int, int, int]] = None) -> None:
@@ -275,6 +357,8 @@ class PopulationRound(_RoundCounter):
     def _set_numerics(self, numerics: str, compression) -> None:
         if numerics not in ("fp32", "tf1"):
             raise ValueError("numerics must be 'fp32' or 'tf1'")
+        if numerics == "tf1" and self._ended_rule is not None:
+            raise ValueError("the training_end rule (set_ended_rule) belongs to the TF2 numerics, not numerics='tf1'")
         self._tf1 = numerics == "tf1"
         if compression is not None and not self._tf1:
             raise ValueError("the compression epilogue belongs to the TF1 (cfa_ongraphs) numerics")
@@ -305,12 +389,30 @@ class PopulationRound(_RoundCounter):
     def run(self, stream=None) -> torch.Tensor:
         """One round: every device's mix of ``models`` into ``out``."""
         self._launch(self.models, self.out, self.src, self.dst, stream)
+        if self._propagates():
+            self._keep_flags(stream)
         return self.out
+
+    def _propagates(self) -> bool:
+        return self._ended_rule is not None and self._ended_rule[1]
+
+    def _keep_flags(self, stream=None) -> None:
+        """The flags a round from ``models`` left in the other buffer become ``ended``."""
+        with torch.cuda.stream(stream or torch.cuda.current_stream(self.models.device)):
+            self._flags[0].copy_(self._flags[1])
 
     def _launch(self, models, out, src, dst, stream=None) -> None:
         if self.tables is None:
             raise RuntimeError("set_topology() or set_schedule() first")
         D, P = models.shape
+        if self._ended_rule is not None:
+            code, propagate = self._ended_rule
+            # propagated flags rotate with models / out; otherwise only set_ended writes them
+            cur = 0 if models is self.models or not propagate else 1
+            self.engine.population_ended(dst, src, *self.tables, self._flags[cur],
+                                         self._flags[cur ^ 1] if propagate else None, self._flags[2], code, D, P,
+                                         *(self._sched or (None, None)), stream)
+            return
         if self._sched is not None:
             if self._tf1:
                 mode, cb, ce = self._compress
@@ -358,6 +460,8 @@ class PopulationRound(_RoundCounter):
             self._graphs.run(R)
         if R & 1:
             self.models.copy_(self.out)
+            if self._propagates():
+                self._keep_flags()
         return self.models
 
     def _step_pair(self, parity: int) -> None:

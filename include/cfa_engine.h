@@ -142,6 +142,14 @@ enum {
   CFA_CLIENT_MIX = 2   /* every device mixes it in: w <- w + (u_c * (g - w)) / d_c */
 };
 
+/* What a device does with the first neighbour that reports training_end
+ * (cfa_mix_population_ended_f32). */
+enum {
+  CFA_ENDED_COPY = 0,        /* takes that neighbour's model as it is          consensus_v3.py:147-152 */
+  CFA_ENDED_TRUNCATE = 1,    /* mixes the collected prefix, the table's eps    consensus_v4.py:234-248 */
+  CFA_ENDED_TRUNCATE_EPS = 2 /* mixes it with eps = 1 / (prefix length + 1)    consensus_v3.py:233 */
+};
+
 CFA_API int cfa_version(void);
 CFA_API const char* cfa_last_error(void);
 
@@ -591,6 +599,37 @@ CFA_API int cfa_mix_population_sched_tf1_f32(float* const* out_ptrs, const float
                                              unsigned long long* round, int D, size_t P, int mode,
                                              size_t cbegin, size_t cend, unsigned long long* kept_counts,
                                              void* stream);
+
+/* (a5/a6 batched) Population round with the TF2 protocol's training_end rule, the flags on the
+ * device: cfa_mix_population_f32 (CFA_RULE_SEQUENTIAL, the same CSR layout, the same three
+ * roundings per step) where nobody has ended, and with no host work between rounds where somebody
+ * has. ended [D] (DEVICE int32, the round's input): device d has reported training_end. Per device:
+ *   ended[d] != 0: out[d] is a bit copy of its own row (it has left its loop,
+ *       federated_learning_keras_consensus_FL_threads_MNIST.py:501-546), saw[d] = 0.
+ *   otherwise the device collects its list in order and stops after the first flagged neighbour,
+ *   at list position f (consensus_v3.py:139-141; consensus_v4.py:191-193, :234-236):
+ *     CFA_ENDED_COPY, f found: out[d] is a bit copy of that neighbour's row, loaded and stored
+ *         with no arithmetic (consensus_v3.py:147-152, consensus_v4.py:205-210).
+ *     CFA_ENDED_TRUNCATE, f found: the fold of positions 0..f with the table's coefficients
+ *         (consensus_v4.py:248: the caller's eps).
+ *     CFA_ENDED_TRUNCATE_EPS, f found or not: the fold of m positions, m = f + 1 or the whole
+ *         list, every step with (float)(1.0 / (double)(m + 1)) (consensus_v3.py:233, as numpy
+ *         applies the Python float to fp32 arrays).
+ *     COPY and TRUNCATE without a flagged neighbour: the table's mix, as cfa_mix_population_f32.
+ *   saw[d] = 1 if a flagged neighbour was found, else 0 (getTrainingStatusFromNeightbor());
+ *   ended_next[d] = ended[d] | saw[d]. Both are DEVICE int32 [D] or NULL, and must not overlap
+ *   ended: the launch reads only ended and writes these two.
+ * sched == NULL and round == NULL: one table (S and T unused). Otherwise both are given and the
+ * call is scheduled as cfa_mix_population_sched_f32: table sched[*round mod S], *round left one
+ * higher in stream order. CFA_E_INVALID: an unknown ended_rule, a null ended, ended_next or saw
+ * overlapping ended, a null table, D < 0 or D > 65535, sched without round or round without sched,
+ * S <= 0 or T <= 0 under a schedule. D == 0 or P == 0: CFA_OK, and the counter is NOT advanced. */
+CFA_API int cfa_mix_population_ended_f32(float* const* out_ptrs, const float* const* src_ptrs,
+                                         const int32_t* csr_ptr, const int32_t* csr_idx,
+                                         const float* csr_coef, const int32_t* sched, int S, int T,
+                                         unsigned long long* round, const int32_t* ended,
+                                         int32_t* ended_next, int32_t* saw, int ended_rule, int D,
+                                         size_t P, void* stream);
 
 /* (f1 batched) FedAvg parameter-server round on a device-resident population, one launch per
  * round: the server's fold of the round's active devices into the global model, then every
