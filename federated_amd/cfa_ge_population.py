@@ -32,6 +32,7 @@ from . import _lib
 from ._graphs import RoundGraphs
 from .consensus import _tf1
 from .engine import Engine
+from .local_training import LocalTrainingHooks
 
 
 def _flat_shapes(ml_model: int, geom: dict, classes: int):
@@ -43,7 +44,7 @@ def _flat_shapes(ml_model: int, geom: dict, classes: int):
             (geom["intermediate_nodes"], classes), (classes,)]
 
 
-class CfaGePopulation:
+class CfaGePopulation(LocalTrainingHooks):
     """D CFA-GE devices resident on one GPU: models, published models, MEWMA states and the
     gradient exchange buffers, advanced one fast-negotiation round per ``round()``."""
 
@@ -171,6 +172,14 @@ class CfaGePopulation:
         self.W, self.pub, self.mixed = b[self._rot], b[(self._rot + 1) % 3], b[(self._rot + 2) % 3]
         self.G, self.G_next = self.G_next, self.G
         self._gpar ^= 1
+
+    # local training between rounds (``set_local_training``, ``epoch``, ``epochs``): the devices train
+    # on W; an epoch advances the same rotation as a round
+    def _training_stack(self) -> torch.Tensor:
+        return self.W
+
+    def _epoch_period(self):
+        return 6, lambda: (self._rot, self._gpar)
 
     def rounds(self, R: int, graph: bool = True) -> None:
         """R consecutive ``round()`` calls on the current stream. ``graph=True`` replays

@@ -17,11 +17,9 @@
 // barriers between the phases. fp32 throughout, like the reference's placeholders.
 #include <algorithm>
 
-#include "cfa_internal.h"
+#include "cfa_grad_common.h"
 
 namespace {
-
-constexpr float kClipLo = 1e-15f, kClipHi = 0.99f;
 
 // Phase timestamps for tools/probe/grad_phases.hip (compiled out of the library).
 #ifdef CFA_GRAD_PHASES
@@ -54,12 +52,6 @@ __device__ __forceinline__ unsigned long long* phase_lds() {
   } while (0)
 #endif
 
-__host__ __device__ inline int same_left(int L, int k, int s) {
-  const int out = (L + s - 1) / s;
-  const int total = max((out - 1) * s + k - L, 0);
-  return total / 2;
-}
-
 // Softmax + clipped cross-entropy backward, in place on logits z[nb][C] -> d logits:
 // d cost / d pred_c = -(y_c / clip(pred_c)) / B where the clip passes the gradient; then the
 // softmax gradient (dp - sum(dp * p)) * p (TF SoftmaxGrad). One lane per class: a sample's
@@ -86,30 +78,6 @@ __device__ void softmax_xent_backward(float* z, const float* y, int nb, int C, i
   }
 }
 
-// lanes per sample of softmax_xent_backward: the power of two >= C (C <= 64, checked on the host)
-inline int softmax_width(int C) {
-  int w = 1;
-  while (w < C) w <<= 1;
-  return w;
-}
-
-constexpr int kGradBlock = 512;  // 8 waves: these graphs are latency-bound, not ALU-bound
-
-// Copy n floats global -> LDS with every load of a thread issued before its first store (the
-// graphs are tiny, so serialized global latency, not bandwidth, would dominate). The tail is
-// predicated rather than looped, so a copy of up to U * T floats is one round trip.
-__device__ __forceinline__ void stage(float* dst, const float* src, int n, int tid, int T) {
-  constexpr int U = 8;
-  for (int i = tid; i < n; i += U * T) {
-    float v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = i + u * T < n ? src[i + u * T] : 0.f;
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-      if (i + u * T < n) dst[i + u * T] = v[u];
-  }
-}
-
 // stage() of three segments with all their loads in flight together.
 __device__ __forceinline__ void stage3(float* d0, const float* s0, int n0, float* d1, const float* s1, int n1,
                                        float* d2, const float* s2, int n2, int tid, int T) {
@@ -133,8 +101,6 @@ __device__ __forceinline__ void stage3(float* d0, const float* s0, int n0, float
     }
   }
 }
-
-constexpr int kMaxTaps = 32;  // conv filter taps held in registers (larger filters read LDS)
 
 struct CnnDims {
   int B, L, C, F, NC, S;
@@ -553,34 +519,6 @@ __global__ __launch_bounds__(kGradBlock) void grad_2nn_kernel(const float* __res
     __syncthreads();
     PHASE(17);
   }
-}
-
-// Raise a kernel's dynamic-LDS limit to `bytes` once per (kernel, device); false if refused.
-bool raise_lds_limit(const void* kernel, int bytes) {
-  static const void* keys[8] = {nullptr};
-  static int granted[8][64] = {{0}};  // per kernel slot and device: the limit granted so far
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
-  int slot = -1;
-  for (int i = 0; i < 8 && dev >= 0; ++i) {
-    const void* k = __atomic_load_n(&keys[i], __ATOMIC_ACQUIRE);
-    if (k == kernel) { slot = i; break; }
-    if (!k) {
-      const void* expected = nullptr;
-      if (__atomic_compare_exchange_n(&keys[i], &expected, kernel, false, __ATOMIC_ACQ_REL, __ATOMIC_ACQUIRE) ||
-          expected == kernel) {
-        slot = i;
-        break;
-      }
-    }
-  }
-  if (slot >= 0 && __atomic_load_n(&granted[slot][dev], __ATOMIC_RELAXED) >= bytes) return true;
-  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  if (slot >= 0) __atomic_store_n(&granted[slot][dev], bytes, __ATOMIC_RELAXED);
-  return true;
 }
 
 // Samples per chunk for `fixed` + Bc * `per_sample` floats of LDS; sets *bytes. 0 if not even one fits.

@@ -127,6 +127,11 @@ inline int device_lds_max() { return device_attr(1, hipDeviceAttributeMaxSharedM
 
 // cfa_grad.hip: per-device LDS query and kernel LDS limits, done ahead of any capture.
 int grad_prepare_device();
+// cfa_local_sgd.hip: the same for the local-SGD kernels.
+int local_sgd_prepare_device();
+// cfa_population.hip: one-thread launch that leaves a device counter (a schedule's round, a cost
+// log's epoch) one higher, in stream order.
+int advance_counter(unsigned long long* counter, hipStream_t st);
 
 namespace {
 

@@ -36,7 +36,8 @@ extern "C" int cfa_device_prepare(int device) {
   CFA_HIP_CHECK(hipGetDevice(&prev));
   if (device != prev) CFA_HIP_CHECK(hipSetDevice(device));
   (void)device_cus();  // fills the shared CU-count cache
-  const int rc = grad_prepare_device();
+  int rc = grad_prepare_device();
+  if (rc == CFA_OK) rc = local_sgd_prepare_device();
   if (device != prev) CFA_HIP_CHECK(hipSetDevice(prev));
   return rc;
 }

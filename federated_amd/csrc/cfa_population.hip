@@ -698,10 +698,11 @@ static int sched_args(const int32_t* sched, int S, int T, unsigned long long* ro
   return CFA_OK;
 }
 // The round is over: the next launch on the stream reads the counter one higher.
-static int advance_round(const SchedArgs& sc, hipStream_t st) {
-  round_advance_kernel<<<1, 1, 0, st>>>(sc.round);
+int advance_counter(unsigned long long* counter, hipStream_t st) {
+  round_advance_kernel<<<1, 1, 0, st>>>(counter);
   return check_launch("round_advance");
 }
+static int advance_round(const SchedArgs& sc, hipStream_t st) { return advance_counter(sc.round, st); }
 
 static int population_tf1(float* const* out_ptrs, const float* const* src_ptrs, const int32_t* csr_ptr,
                           const int32_t* csr_idx, const double* csr_coef, const SchedArgs& sc, int D,

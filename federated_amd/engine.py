@@ -496,6 +496,63 @@ class Engine:
             raise ValueError("ml_model must be 1 (CNN) or 2 (2NN)")
         return grads
 
+    # -- local training between rounds (f3/f4) ----------------------------------------------
+    def local_sgd(self, ml_model: int, x: torch.Tensor, y: torch.Tensor, models: torch.Tensor, geom: dict,
+                  batch_stride: int, batch_rows: int, steps: int, lr: float, update: bool = True,
+                  cost: Optional[torch.Tensor] = None, cost_log: Optional[torch.Tensor] = None,
+                  epoch: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+        """One local epoch of minibatch SGD for every device in one launch
+        (cfa_local_sgd_{cnn,2nn}_f32): device d steps row d of ``models`` [D, P] (fp32 CUDA, unit
+        element stride, any row pitch; TF1 order W1 b1 W2 b2) through ``steps`` minibatches of its
+        own samples x [D, Ns, L] / y [D, Ns, C], minibatch i = rows [i * batch_stride,
+        i * batch_stride + batch_rows), with w <- w - lr * grad. ``update=False`` is the validation
+        pass: forward only, ``models`` untouched. ``cost`` [D] fp64 CUDA receives each device's
+        mean minibatch cost. ``cost_log`` [cap, D] fp64 CUDA and ``epoch`` (one-element int64
+        CUDA counter), given together: the cost also goes to row min(epoch, cap - 1) of the log
+        and the counter is left one higher, in stream order. ``geom`` as ``grad_rows``."""
+        D, Ns, L = _check_nd(x, "x", 3)
+        Dy, Nsy, C = _check_nd(y, "y", 3)
+        Dm, P = _check_nd(models, "models", pitched=True)
+        if (Dy, Nsy) != (D, Ns) or Dm != D:
+            raise ValueError("x [D, Ns, L], y [D, Ns, C] and models [D, P] must agree on D and Ns")
+        batch_stride, batch_rows, steps = int(batch_stride), int(batch_rows), int(steps)
+        if steps < 1 or batch_rows < 1 or batch_stride < 1:
+            raise ValueError("steps, batch_rows and batch_stride must be >= 1")
+        if (steps - 1) * batch_stride + batch_rows > Ns:
+            raise ValueError(f"minibatch {steps - 1} ends at row {(steps - 1) * batch_stride + batch_rows} "
+                             f"of {Ns} samples")
+        if cost is not None:
+            _check_bucket(cost, "cost", D, torch.float64)
+        if (cost_log is None) != (epoch is None):
+            raise ValueError("cost_log and epoch are given together or not at all")
+        cap = 0
+        if cost_log is not None:
+            _check_tables(("cost_log", cost_log, torch.float64), ("epoch", epoch, torch.int64))
+            if cost_log.dim() != 2 or cost_log.shape[1] != D or cost_log.shape[0] < 1 or epoch.numel() != 1:
+                raise ValueError("cost_log must be [cap >= 1, D] and epoch a one-element counter")
+            cap = int(cost_log.shape[0])
+        pitch = int(models.stride(0)) if D > 1 else P
+        if pitch < P:
+            raise ValueError("models rows overlap (pitch below P)")
+        tail = (pitch, D, batch_stride, batch_rows, steps, float(lr), int(bool(update)),
+                cost.data_ptr() if cost is not None else None,
+                cost_log.data_ptr() if cost_log is not None else None, cap,
+                epoch.data_ptr() if epoch is not None else None, self.stream_handle(stream))
+        if ml_model == 1:
+            F, NC, S = int(geom["filter"]), int(geom["number"]), int(geom["stride"])
+            L2 = -(-(-(-L // S)) // S)
+            if P != F * NC + NC + L2 * NC * C + C:
+                raise ValueError("CNN bucket size does not match the geometry")
+            _lib.call("cfa_local_sgd_cnn_f32", x.data_ptr(), y.data_ptr(), Ns, L, C, F, NC, S, models.data_ptr(), *tail)
+        elif ml_model == 2:
+            H = int(geom["intermediate_nodes"])
+            if P != L * H + H + H * C + C:
+                raise ValueError("2NN bucket size does not match the geometry")
+            _lib.call("cfa_local_sgd_2nn_f32", x.data_ptr(), y.data_ptr(), Ns, L, H, C, models.data_ptr(), *tail)
+        else:
+            raise ValueError("ml_model must be 1 (CNN) or 2 (2NN)")
+        return models
+
     # -- population ------------------------------------------------------------------------
     def mix_window(self, outs: Sequence[torch.Tensor], rows: Sequence[torch.Tensor], alphas: Sequence[Sequence[float]],
                    hl: int, hr: int, stream=None) -> None:

@@ -23,6 +23,7 @@ from . import _lib
 from .consensus import _tf1, _tf2
 from ._graphs import RoundGraphs
 from .engine import Engine
+from .local_training import LocalTrainingHooks
 
 RULE_SEQUENTIAL = 0
 # auto-select the window round above this bucket size: below it the whole population sits in
@@ -203,6 +204,7 @@ class _RoundCounter:
     def _new_schedule(self, sched: torch.Tensor) -> None:
         self._sched = (sched, torch.zeros(1, dtype=torch.int64, device=sched.device))
         self._graphs = None
+        self._epoch_graphs = None
 
     def reset_round(self, r: int = 0) -> None:
         """The next round is round ``r`` (it mixes with table sched[r % S]); written in the order
@@ -475,7 +477,7 @@ class PopulationRound(_RoundCounter):
         self._parity ^= 1
 
 
-class Tf1PopulationRound(_RoundCounter):
+class Tf1PopulationRound(_RoundCounter, LocalTrainingHooks):
     """A device-resident population on the TF1 protocol (cfa.py:105-154, cfa_ongraphs.py): at
     epoch e every device mixes its own epoch-e model with the models its neighbours PUBLISHED at
     epoch e-1 (their pre-mix inputs of e-1, cfa.py:131-139), with the TF1 numerics (fp64 chain,
@@ -536,6 +538,7 @@ class Tf1PopulationRound(_RoundCounter):
                           for a in schedule_csr([lists], policy, self.D, neighbor_base=self.D, **self._LAYOUT))
         self._sched = None
         self._graphs = None  # captured rounds hold the tables they were captured with
+        self._epoch_graphs = None
 
     def set_schedule(self, lists_per_table, policy, sched: Optional[Sequence[int]] = None,
                      compression: Optional[Tuple[int, int, int]] = None) -> None:
@@ -572,6 +575,14 @@ class Tf1PopulationRound(_RoundCounter):
             self.engine.population_tf1(dst, src, *self._csr, self.D, self.P, stream, mode, cb, ce,
                                        self.kept if mode else None)
         self._rot = (self._rot + 2) % 3  # (current, previous, out) <- (out, current, previous)
+
+    # local training between rounds (``set_local_training``, ``epoch``, ``epochs``): the devices train
+    # on ``current``; an epoch advances the same rotation as a round
+    def _training_stack(self) -> torch.Tensor:
+        return self.current
+
+    def _epoch_period(self):
+        return 3, lambda: self._rot
 
     def rounds(self, R: int, graph: bool = True) -> None:
         """R rounds; ``graph=True`` replays captured 3-round periods (hipGraph), same results."""

@@ -545,6 +545,38 @@ CFA_API int cfa_ge_grad_2nn_rows_f32(const float* x, const float* y, int B, int 
                                      const int32_t* data_row, float* grads, float* workspace,
                                      size_t workspace_elems, int M, void* stream);
 
+/* (f3/f4) Local training between two rounds: one epoch of plain minibatch SGD for every device
+ * of a TF1 population in one launch (federated_sample_CNN_CFA-GE.py:137-173, the assignment
+ * W <- W_ext - learning_rate * grad :114-118; federated_sample_2NN_CFA.py:97-101), on the two
+ * graphs and the cost of the cfa_ge_grad_* block above. x [D, Ns, L] and y [D, Ns, classes] are
+ * every device's samples and one-hot labels; models is a [D, pitch] stack of model buckets in
+ * the TF1 order (W1, b1, W2, b2), pitch >= P floats, all device fp32 arrays. One workgroup owns
+ * device d for the whole launch and keeps its model in LDS:
+ *   w = models[d]
+ *   for i in 0 .. steps-1: minibatch i = sample rows [i*batch_stride, i*batch_stride + batch_rows)
+ *       c_i = cost(w; minibatch i), a mean over batch_rows
+ *       update != 0:  w <- w - lr * d cost / d w      (fp32)
+ *   update != 0:  models[d] = w      (update == 0: the validation pass :163-172, forward only,
+ *                                     models untouched)
+ *   cost[d] = sum_i c_i / steps      (fp64, like the driver's Python float; cost may be NULL)
+ * The driver's slice i*batch_size : (i+1)*batch_size - 1 is batch_stride 5, batch_rows 4.
+ * cost_log [log_cap, D] (fp64) and epoch (one device counter) are given together or both NULL:
+ * with them the launch also writes cost[d] to row min(*epoch, log_cap-1) of cost_log and leaves
+ * *epoch one higher in stream order, so a replayed graph of many epochs leaves the whole curve
+ * on the device. Deterministic: every output has one owner, every sum a fixed order.
+ * CFA_E_INVALID: steps, batch_rows or batch_stride < 1, a minibatch past Ns, pitch < P, a null
+ * x / y / models. CFA_E_UNSUPPORTED: the model, two minibatches and their activations exceed
+ * one workgroup's LDS (raised to the device's 160 KiB by cfa_device_prepare), or classes > 64. */
+CFA_API int cfa_local_sgd_cnn_f32(const float* x, const float* y, int Ns, int L, int classes, int filter,
+                                  int number, int stride, float* models, size_t pitch, int D,
+                                  int batch_stride, int batch_rows, int steps, float lr, int update,
+                                  double* cost, double* cost_log, int log_cap, unsigned long long* epoch,
+                                  void* stream);
+CFA_API int cfa_local_sgd_2nn_f32(const float* x, const float* y, int Ns, int L, int hidden, int classes,
+                                  float* models, size_t pitch, int D, int batch_stride, int batch_rows,
+                                  int steps, float lr, int update, double* cost, double* cost_log,
+                                  int log_cap, unsigned long long* epoch, void* stream);
+
 /* (a1-a6 batched) Population round: one launch mixes D devices.
  * For device d, CSR entries e in [csr_ptr[d], csr_ptr[d+1]) list its sources in order; the
  * FIRST entry is the device's own (local) bucket. Source e is src_ptrs[csr_idx[e]], output d
