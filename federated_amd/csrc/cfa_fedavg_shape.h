@@ -1,5 +1,5 @@
 // cfa_fedavg_shape.h — host-only launch-shape rules of the FedAvg population round
-// (cfa_fedavg_population_round_f32, cfa_population.hip). No HIP in here; the tests read the
+// (cfa_fedavg_population_round_f32, cfa_fedavg.hip). No HIP in here; the tests read the
 // constants below to place their sizes on the kernel's tile and batch boundaries.
 #pragma once
 

@@ -4,7 +4,8 @@
 // definition of each mixing rule's step (seq_step, div_step, lin_step, tf1_first / tf1_step,
 // div_step_f64, mewma_step, mewma_step_f64, split_sum) that every kernel of the library calls,
 // the fold of the sequential / linear / FedAvg rules, the tile walk (TileWalk) and the fan-in
-// dispatch (dispatch_fanin) of the streaming kernels, the compression epilogue, and the
+// dispatch (dispatch_fanin) of the streaming kernels, the compression epilogue, what the rounds
+// of cfa_population.hip and cfa_fedavg.hip share (SchedArgs, sched_slot, first_flagged), and the
 // thread-local error reporting behind cfa_last_error(). The host-only launch rules (shape bands,
 // bucket split, passes) are in cfa_mix_shape.h. Every .hip file of the library
 // is compiled with -ffp-contract=off: CFA_RULE_SEQUENTIAL evaluates t = x - w; t = a * t;
@@ -604,4 +605,49 @@ static int validate_mix(const float* out, const float* local, const float* const
 static bool needs_ref(int mode) {
   return mode == CFA_COMPRESS_SPARSE_DPCM || mode == CFA_COMPRESS_SPARSE_DPCM_HI;
 }
+
+// ------------------------------------------------------------------------------------------
+// Rounds of a device-resident population (cfa_population.hip, cfa_fedavg.hip).
+// ------------------------------------------------------------------------------------------
+// A schedule: round r works on table sched[r mod S] of T tables. The round counter is a device
+// word, so a captured period of rounds replays with another table each time. Every workgroup of a
+// round reads the same counter: advance_round raises it after the round, in stream order.
+struct SchedArgs {
+  const int32_t* sched;       // [S] table index of each slot
+  unsigned long long* round;  // the round counter
+  unsigned S;
+};
+
+// The table index of the current round: one chain of uniform loads (round -> sched).
+__device__ __forceinline__ int sched_slot(const SchedArgs& sc) {
+  const unsigned long long r = *static_cast<const unsigned long long*>(sc.round);
+  return sc.sched[r % sc.S];
+}
+
+// The first entry of idx[b, e) whose device is flagged, e when there is none: the workgroup's
+// lanes take one entry each per pass and keep the smallest flagged position. Called by every lane
+// of the workgroup (it synchronises).
+__device__ __forceinline__ int first_flagged(const int32_t* flags, const int32_t* idx, int b, int e) {
+  __shared__ int first;
+  if (threadIdx.x == 0) first = e;
+  __syncthreads();
+  for (int k = b + (int)threadIdx.x; k < e; k += kBlock)
+    if (flags[idx[k]]) {
+      atomicMin(&first, k);
+      break;
+    }
+  __syncthreads();
+  return __builtin_amdgcn_readfirstlane(first);
+}
+
+// A scheduled entry's own arguments, checked before anything else; sc.sched == nullptr stands for
+// the static entry points' one table.
+static int sched_args(const int32_t* sched, int S, int T, unsigned long long* round, SchedArgs& sc) {
+  if (S <= 0 || T <= 0) return fail(CFA_E_INVALID, "schedule of %d slots over %d tables", S, T);
+  if (!sched || !round) return fail(CFA_E_INVALID, "null schedule or round counter");
+  sc = SchedArgs{sched, round, (unsigned)S};
+  return CFA_OK;
+}
+// The round is over: the next launch on the stream reads the counter one higher.
+static int advance_round(const SchedArgs& sc, hipStream_t st) { return advance_counter(sc.round, st); }
 }  // namespace

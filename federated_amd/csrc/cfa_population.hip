@@ -1,16 +1,11 @@
-// cfa_population.hip — whole-population rounds: the CSR one-launch kernel
-// (cfa_mix_population_f32; _sched_f32 with a table per round; _ended_f32 with the training_end
-// rule on device-resident flags) and the sliding-window passes (cfa_mix_window_f32) that load each
-// row of a ring window once for up to 8 consecutive devices, and the sliding ring round
-// (cfa_mix_ring_slide_f32) that reads every row of a run of ring devices once, the FedAvg
-// parameter-server round (cfa_fedavg_population_round_f32), and the CFA-GE population step. Every
-// rule's step (seq_step, div_step, lin_step, tf1_first / tf1_step, mewma_step, split_sum) is the
-// one definition of cfa_internal.h.
-#include <type_traits>
-
+// cfa_population.hip — the CSR rounds of a whole population in one launch: cfa_mix_population_f32
+// (_sched_f32 with a table per round; _ended_f32 with the training_end rule on device-resident
+// flags; _tf1_f32 / _sched_tf1_f32 with the TF1 numerics), the CFA-GE population step, and the
+// round counter's advance. The ring family is in cfa_ring.hip, the FedAvg round in
+// cfa_fedavg.hip. Every rule's step (seq_step, lin_step, tf1_first / tf1_step, mewma_step,
+// split_sum) is the one definition of cfa_internal.h, as are the schedule lookup (sched_slot) and
+// the scan for the first flagged neighbour (first_flagged).
 #include "cfa_internal.h"
-#include "cfa_fedavg_shape.h"
-#include "cfa_slide_shape.h"
 
 // Resident workgroups per CU across a whole population launch (all devices together). 8 by
 // default; CFA_POP_WG_PER_CU overrides it per call (read at each launch, so one process can
@@ -83,51 +78,27 @@ __device__ __forceinline__ void population_fold(float* out, const float* const* 
   }
 }
 
-// csr_ptr is the round's table: D + 1 row offsets into csr_idx / csr_coef.
-template <int RULE>
-__device__ __forceinline__ void population_body(float* const* out_ptrs, const float* const* src_ptrs,
-                                                const int32_t* csr_ptr, const int32_t* csr_idx,
-                                                const float* csr_coef, long long nvec, long long P) {
-  const int d = blockIdx.y;
-  population_fold<RULE>(out_ptrs[d], src_ptrs, csr_idx, csr_coef, csr_ptr[d], csr_ptr[d + 1], false, 0.f, nvec, P);
+// The round's table, D + 1 row offsets into csr_idx / csr_coef: csr_ptr itself, or under a
+// topology schedule (SCHED: cfa_mix_population_sched_f32 / _sched_tf1_f32 / _ended_f32) table
+// sched[r mod S] of the T tables that lie back to back in csr_ptr, their offsets absolute in the
+// shared csr_idx / csr_coef. The lookup is one chain of uniform loads (round -> sched -> the
+// table's base) ahead of the tile loop; a static round does not read `sc`.
+template <bool SCHED>
+__device__ __forceinline__ const int32_t* round_table(const int32_t* csr_ptr, const SchedArgs& sc) {
+  if constexpr (SCHED) return csr_ptr + (long long)sched_slot(sc) * ((long long)gridDim.y + 1);  // grid.y = D
+  else return csr_ptr;
 }
 
-template <int RULE>
+template <int RULE, bool SCHED>
 __global__ __launch_bounds__(kBlock) void population_kernel(float* const* out_ptrs,
                                                             const float* const* src_ptrs,
                                                             const int32_t* csr_ptr,
                                                             const int32_t* csr_idx,
-                                                            const float* csr_coef,
+                                                            const float* csr_coef, SchedArgs sc,
                                                             long long nvec, long long P) {
-  population_body<RULE>(out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, nvec, P);
-}
-
-// Topology schedule (cfa_mix_population_sched_f32 / _sched_tf1_f32): T tables of D + 1 row offsets
-// lie back to back in csr_ptr, their offsets absolute in the shared csr_idx / csr_coef, and round r
-// mixes with table sched[r mod S]. The round counter is a device word, so a captured period of
-// rounds replays with another table each time. Every workgroup of a round reads the same counter:
-// round_advance_kernel raises it after the mix, in stream order. The lookup is one chain of
-// uniform loads (round -> sched -> the table's base) ahead of the tile loop.
-struct SchedArgs {
-  const int32_t* sched;       // [S] table index of each slot
-  unsigned long long* round;  // the round counter
-  unsigned S;
-};
-
-__device__ __forceinline__ const int32_t* sched_table(const int32_t* csr_ptr, const SchedArgs& sc) {
-  const unsigned long long r = *static_cast<const unsigned long long*>(sc.round);
-  const int t = sc.sched[r % sc.S];
-  return csr_ptr + (long long)t * ((long long)gridDim.y + 1);  // grid.y = D
-}
-
-template <int RULE>
-__global__ __launch_bounds__(kBlock) void population_sched_kernel(float* const* out_ptrs,
-                                                                  const float* const* src_ptrs,
-                                                                  const int32_t* csr_ptr,
-                                                                  const int32_t* csr_idx,
-                                                                  const float* csr_coef, SchedArgs sc,
-                                                                  long long nvec, long long P) {
-  population_body<RULE>(out_ptrs, src_ptrs, sched_table(csr_ptr, sc), csr_idx, csr_coef, nvec, P);
+  const int32_t* ptr = round_table<SCHED>(csr_ptr, sc);
+  const int d = blockIdx.y;
+  population_fold<RULE>(out_ptrs[d], src_ptrs, csr_idx, csr_coef, ptr[d], ptr[d + 1], false, 0.f, nvec, P);
 }
 
 __global__ void round_advance_kernel(unsigned long long* round) { *round += 1; }
@@ -148,22 +119,6 @@ struct EndedArgs {
   int rule;
 };
 
-// The first entry of [b, e) whose device is flagged, e when there is none: the workgroup's lanes
-// take one entry each per pass and keep the smallest flagged position (as fedavg_round_lookup).
-// Called by every lane of the workgroup (it synchronises).
-__device__ __forceinline__ int first_ended(const int32_t* ended, const int32_t* csr_idx, int b, int e) {
-  __shared__ int first;
-  if (threadIdx.x == 0) first = e;
-  __syncthreads();
-  for (int k = b + (int)threadIdx.x; k < e; k += kBlock)
-    if (ended[csr_idx[k]]) {
-      atomicMin(&first, k);
-      break;
-    }
-  __syncthreads();
-  return __builtin_amdgcn_readfirstlane(first);
-}
-
 template <bool SCHED>
 __global__ __launch_bounds__(kBlock) void population_ended_kernel(float* const* out_ptrs,
                                                                   const float* const* src_ptrs,
@@ -171,13 +126,12 @@ __global__ __launch_bounds__(kBlock) void population_ended_kernel(float* const* 
                                                                   const int32_t* csr_idx,
                                                                   const float* csr_coef, SchedArgs sc,
                                                                   EndedArgs ea, long long nvec, long long P) {
-  const int32_t* ptr = csr_ptr;
-  if constexpr (SCHED) ptr = sched_table(csr_ptr, sc);
+  const int32_t* ptr = round_table<SCHED>(csr_ptr, sc);
   const int d = blockIdx.y;
   int e0 = ptr[d], e1 = ptr[d + 1];
   const bool self = ea.ended[d] != 0;  // uniform over the device's workgroups, as everything below
   int f = e1;
-  if (!self) f = first_ended(ea.ended, csr_idx, e0 + 1, e1);
+  if (!self) f = first_flagged(ea.ended, csr_idx, e0 + 1, e1);
   const bool found = f < e1;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     if (ea.saw) ea.saw[d] = found;
@@ -259,479 +213,69 @@ __device__ __forceinline__ void population_tf1_body(float* const* out_ptrs, cons
   if (cp.mode) block_add_count(kept, cp.kept + d);
 }
 
+template <bool SCHED>
 __global__ __launch_bounds__(kBlock) void population_tf1_kernel(float* const* out_ptrs,
                                                                 const float* const* src_ptrs,
                                                                 const int32_t* csr_ptr,
                                                                 const int32_t* csr_idx,
-                                                                const double* csr_coef,
+                                                                const double* csr_coef, SchedArgs sc,
                                                                 long long nvec, long long P,
                                                                 CompressParams cp) {
-  population_tf1_body(out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, nvec, P, cp);
-}
-
-__global__ __launch_bounds__(kBlock) void population_tf1_sched_kernel(float* const* out_ptrs,
-                                                                      const float* const* src_ptrs,
-                                                                      const int32_t* csr_ptr,
-                                                                      const int32_t* csr_idx,
-                                                                      const double* csr_coef, SchedArgs sc,
-                                                                      long long nvec, long long P,
-                                                                      CompressParams cp) {
-  population_tf1_body(out_ptrs, src_ptrs, sched_table(csr_ptr, sc), csr_idx, csr_coef, nvec, P, cp);
-}
-
-// ------------------------------------------------------------------------------------------
-// Sliding-window population pass (cfa_mix_window_f32): nb <= 8 consecutive devices of a ring
-// window (hl below, hr above) share their rows, so each row of the window is loaded ONCE per
-// element for all nb devices: (nb + hl + hr) reads + nb writes instead of nb * (hl + hr + 2).
-// Device b's local row is rows[b + hl]; its neighbours, in the reference window's order
-// (g-hl .. g-1, g+1 .. g+hr), are rows[b .. b+hl-1], rows[b+hl+1 .. b+hl+hr].
-// ------------------------------------------------------------------------------------------
-constexpr int kWinMaxDev = 8;
-struct WindowArgs {
-  const float* rows[kWinMaxDev + 8];
-  float* out[kWinMaxDev];
-  float a[kWinMaxDev];  // one coefficient per device, used for each of its steps
-  int nb;
-};
-
-// The fold of one ring device over its window's HL + HR + 1 rows, row(j) = the j-th row of the
-// window (the local row is row(HL)): the local row, then the rows below in ascending order, then
-// the rows above, as the reference window's order.
-template <int HL, int HR, typename Row>
-__device__ __forceinline__ f4 ring_fold(Row row, float a) {
-  f4 acc = row(HL);
-#pragma unroll
-  for (int j = 0; j < HL; ++j) acc = seq_step(acc, row(j), a);
-#pragma unroll
-  for (int j = 0; j < HR; ++j) acc = seq_step(acc, row(HL + 1 + j), a);
-  return acc;
-}
-
-template <int HL, int HR, int U, bool SC1>
-__device__ __forceinline__ void window_body(const WindowArgs& w, long long nvec) {
-  constexpr int R = kWinMaxDev + HL + HR;
-  constexpr long long kTile = (long long)kBlock * U;
-  const int nr = w.nb + HL + HR;
-  for (long long t = blockIdx.x; t * kTile < nvec; t += gridDim.x) {
-    const long long base = t * kTile + threadIdx.x;
-    f4 r[U][R];
-#pragma unroll
-    for (int k = 0; k < R; ++k)
-      if (k < nr)
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const long long i = base + (long long)u * kBlock;
-          if (i < nvec) r[u][k] = ld4<true>(w.rows[k], i);
-        }
-#pragma unroll
-    for (int b = 0; b < kWinMaxDev; ++b)
-      if (b < w.nb) {
-        // (unused and removed by the compiler when !SC1) write-through streaming store
-        const __amdgpu_buffer_rsrc_t o = out_rsrc(w.out[b], (unsigned)(nvec * 16));
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const long long i = base + (long long)u * kBlock;
-          if (i < nvec) {
-            const f4 y = ring_fold<HL, HR>([&](int j) { return r[u][b + j]; }, w.a[b]);
-            if constexpr (SC1)
-              st16_buf<kStoreSc1>(o, i, y);
-            else
-              st4<true>(w.out[b], i, y);
-          }
-        }
-      }
-  }
-}
-
-template <int HL, int HR, int U, bool SC1>
-__global__ __launch_bounds__(kBlock) void window_vec_kernel(WindowArgs w, long long nvec) {
-  window_body<HL, HR, U, SC1>(w, nvec);
-}
-
-// A whole ring-window round of a stacked population in ONE launch (cfa_mix_ring_round_f32):
-// grid.y = pass p over devices [8p, 8p + nb); each block derives its pass's rows from the stack
-// base and pitch (row g of the window = in + ((8p - HL + g) mod D) * pitch), then runs the
-// window pass body. Same operations as one cfa_mix_window_f32 launch per pass.
-struct RingArgs {
-  const float* in;
-  float* out;
-  const float* alphas;  // [D] device array, one coefficient per device
-  long long pitch;      // floats between consecutive devices' rows
-  long long off;        // element offset of this launch's chunk
-  int D;
-};
-
-template <int HL, int HR, int U, bool SC1>
-__global__ __launch_bounds__(kBlock) void ring_round_kernel(RingArgs ra, long long nvec) {
-  const int p = blockIdx.y;
-  WindowArgs w;
-  w.nb = min(kWinMaxDev, ra.D - p * kWinMaxDev);
-#pragma unroll
-  for (int k = 0; k < kWinMaxDev + HL + HR; ++k) {
-    const int g = ((p * kWinMaxDev - HL + k) % ra.D + ra.D) % ra.D;
-    w.rows[k] = ra.in + (long long)g * ra.pitch + ra.off;
-  }
-#pragma unroll
-  for (int b = 0; b < kWinMaxDev; ++b) {
-    const int d = min(p * kWinMaxDev + b, ra.D - 1);
-    w.out[b] = ra.out + (long long)d * ra.pitch + ra.off;
-    w.a[b] = ra.alphas[d];
-  }
-  window_body<HL, HR, U, SC1>(w, nvec);
-}
-
-// ------------------------------------------------------------------------------------------
-// Sliding ring round (cfa_mix_ring_slide_f32): every row of a run of consecutive ring devices is
-// read ONCE and every output written once. A workgroup owns a column tile of kBlock * U float4
-// (lane x holds vectors base + v * kBlock, v < U, so each wave instruction is a contiguous 1 KB)
-// and a segment (blockIdx.y) of `seg` consecutive devices. It walks the segment's row stream
-// (rows d0-HL .. d0+len-1+HR, mod `rows`) through a ring of W + PF register slots of U float4,
-// W = HL+HR+1: device m of the segment folds stream rows m .. m+W-1 (its local row is m+HL) while
-// the loads of rows m+W .. m+W-1+PF are in flight. The device loop is unrolled W + PF times, so
-// stream row q always sits in slot q mod (W + PF) and every register index is static. A segment
-// re-reads HL+HR halo rows: a call reads count + segments * (HL+HR) rows. The fold is the window
-// pass's (ring_fold), on the slots the window's rows sit in, per vector.
-// ------------------------------------------------------------------------------------------
-struct SlideArgs {
-  const float* in;
-  float* out;
-  const float* alphas;             // [count] device array, one coefficient per device of the run
-  long long in_pitch, out_pitch;   // floats between consecutive rows
-  long long off;                   // element offset of this launch's chunk
-  int rows, first, count, seg;     // seg: devices per segment
-};
-
-template <int HL, int HR, int PF, int U, bool SC1>
-__global__ __launch_bounds__(kBlock) void ring_slide_kernel(SlideArgs sa, long long nvec) {
-  constexpr int W = HL + HR + 1;
-  constexpr int RS = W + PF;
-  constexpr long long kTile = (long long)kBlock * U;
-  const int n0 = (int)blockIdx.y * sa.seg;  // first device of the segment, relative to sa.first
-  const int len = min(sa.seg, sa.count - n0);
-  const int total = len + HL + HR;  // rows of the segment's stream
-  const int d0 = sa.first + n0;
-  int g0 = (d0 - HL) % sa.rows;
-  if (g0 < 0) g0 += sa.rows;
-  const int o0 = d0 >= sa.rows ? d0 - sa.rows : d0;
-  const float* const in = sa.in + sa.off;
-  float* const out = sa.out + sa.off;
-  const float* const in_end = in + (long long)sa.rows * sa.in_pitch;
-  float* const out_end = out + (long long)sa.rows * sa.out_pitch;
-  for (long long t = blockIdx.x; t * kTile < nvec; t += gridDim.x) {
-    const long long i = t * kTile + threadIdx.x;
-    if (i >= nvec) continue;  // the stripes ascend: a lane without its first vector has none
-    // Byte offsets of the lane's vectors (a chunk is at most kMaxChunkVec float4: below 2^31). In
-    // the last tile a stripe may lie partly or wholly past nvec: such a vector loads the lane's
-    // first vector again (in bounds, so the loads need no branch) and is never stored.
-    bool ok[U];
-    unsigned voff[U];
-#pragma unroll
-    for (int v = 0; v < U; ++v) {
-      ok[v] = i + (long long)v * kBlock < nvec;
-      voff[v] = (unsigned)((ok[v] ? i + (long long)v * kBlock : i) * 16);
-    }
-    const float* rp = in + (long long)g0 * sa.in_pitch;  // next row of the stream to load
-    float* op = out + (long long)o0 * sa.out_pitch;      // next output row
-    f4 r[RS][U];
-    auto load_row = [&](f4(&slot)[U]) {  // all U loads of the stream's next row
-#pragma unroll
-      for (int v = 0; v < U; ++v)
-        slot[v] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(reinterpret_cast<const char*>(rp) + voff[v]));
-      rp += sa.in_pitch;
-      if (rp == in_end) rp = in;
-    };
-#pragma unroll
-    for (int q = 0; q < RS - 1; ++q)
-      if (q < total) load_row(r[q]);
-    for (int n = 0; n < len; n += RS) {
-#pragma unroll
-      for (int u = 0; u < RS; ++u) {
-        const int m = n + u;
-        if (m < len) {
-          // stream row m+W-1+PF: into the slot row m-1 has left
-          if (m + RS - 1 < total) load_row(r[(u + RS - 1) % RS]);
-          const float a = sa.alphas[n0 + m];
-          f4 acc[U];
-#pragma unroll
-          for (int v = 0; v < U; ++v) acc[v] = ring_fold<HL, HR>([&](int j) { return r[(u + j) % RS][v]; }, a);
-#pragma unroll
-          for (int v = 0; v < U; ++v)
-            if (ok[v]) {
-              if constexpr (SC1)
-                st16_buf<kStoreSc1>(out_rsrc(op, (unsigned)(nvec * 16)), i + (long long)v * kBlock, acc[v]);
-              else
-                __builtin_nontemporal_store(acc[v], reinterpret_cast<f4*>(reinterpret_cast<char*>(op) + voff[v]));
-            }
-          op += sa.out_pitch;
-          if (op == out_end) op = out;
-        }
-      }
-    }
-  }
-}
-
-// Scalar window pass (misaligned rows, the < 4-element tail): runtime hl / hr.
-__global__ __launch_bounds__(kBlock) void window_scalar_kernel(WindowArgs w, int hl, int hr,
-                                                               long long begin, long long P) {
-  for (long long i = begin + (long long)blockIdx.x * kBlock + threadIdx.x; i < P;
-       i += (long long)gridDim.x * kBlock) {
-    for (int b = 0; b < w.nb; ++b) {
-      float acc = w.rows[b + hl][i];
-      for (int j = 0; j < hl; ++j) acc = seq_step(acc, w.rows[b + j][i], w.a[b]);
-      for (int j = 0; j < hr; ++j) acc = seq_step(acc, w.rows[b + hl + 1 + j][i], w.a[b]);
-      w.out[b][i] = acc;
-    }
-  }
+  population_tf1_body(out_ptrs, src_ptrs, round_table<SCHED>(csr_ptr, sc), csr_idx, csr_coef, nvec, P, cp);
 }
 
 }  // namespace
 
-namespace {
-struct WindowTune {
-  int vec, sc1, blocks_per_cu;
-};
-static WindowTune window_tune() {  // env overrides for tools/tune_window.py; results identical
-  WindowTune t{1, 0, 6};  // tools/tune_window.py, profiles/r01_tune_window.jsonl
-  t.vec = env_int("CFA_WINDOW_VEC", t.vec) == 1 ? 1 : 2;
-  t.sc1 = env_int("CFA_WINDOW_SC1", t.sc1) ? 1 : 0;
-  t.blocks_per_cu = env_int("CFA_WINDOW_BLOCKS_PER_CU", t.blocks_per_cu);
-  if (t.blocks_per_cu <= 0) t.blocks_per_cu = 2;  // kept as it is: not the default 6
-  return t;
-}
-static long long window_tiles(long long m, const WindowTune& t) {
-  return (m + (long long)kBlock * t.vec - 1) / ((long long)kBlock * t.vec);
-}
-// The run-time (vec, sc1) of a window launch as the kernels' <U, SC1>: fn(U, SC1) gets them as
-// std::integral_constant values.
-template <typename F>
-void for_vec_sc1(const WindowTune& t, F&& fn) {
-  using One = std::integral_constant<int, 1>;
-  using Two = std::integral_constant<int, 2>;
-  if (t.vec == 1) {
-    if (t.sc1) fn(One{}, std::true_type{});
-    else fn(One{}, std::false_type{});
-  } else {
-    if (t.sc1) fn(Two{}, std::true_type{});
-    else fn(Two{}, std::false_type{});
-  }
-}
-template <int HL, int HR>
-void launch_window(const WindowArgs& w, long long nvec, hipStream_t st) {
-  const WindowTune t = window_tune();
-  const cfa_launch_t lc{t.blocks_per_cu, t.vec, 1};
-  for_each_chunk(nvec, [&](long long done, long long m) {
-    WindowArgs c = w;
-    for (int k = 0; k < w.nb + HL + HR; ++k) c.rows[k] = w.rows[k] + done * 4;
-    for (int b = 0; b < w.nb; ++b) c.out[b] = w.out[b] + done * 4;
-    const unsigned grid = grid_for(window_tiles(m, t), lc);
-    for_vec_sc1(t, [&](auto u, auto sc1) {
-      window_vec_kernel<HL, HR, decltype(u)::value, decltype(sc1)::value><<<grid, kBlock, 0, st>>>(c, m);
-    });
-  });
-}
-template <int HL, int HR>
-void launch_ring_round(const RingArgs& ra, long long nvec, hipStream_t st) {
-  const WindowTune t = window_tune();
-  const cfa_launch_t lc{t.blocks_per_cu, t.vec, 1};
-  const unsigned passes = (unsigned)((ra.D + kWinMaxDev - 1) / kWinMaxDev);
-  for_each_chunk(nvec, [&](long long done, long long m) {
-    RingArgs c = ra;
-    c.off = ra.off + done * 4;
-    const long long tiles = window_tiles(m, t);
-    // the launch's blocks over all passes: about blocks_per_cu per CU in all. Not shared_grid_x:
-    // the tiles are capped before the division by the passes (10 tiles over 16 passes give 1, not 10)
-    long long gx = (grid_for(tiles, lc) + passes - 1) / passes;
-    if (gx < 1) gx = 1;
-    if (gx > tiles) gx = tiles;
-    const dim3 grid((unsigned)gx, passes);
-    for_vec_sc1(t, [&](auto u, auto sc1) {
-      ring_round_kernel<HL, HR, decltype(u)::value, decltype(sc1)::value><<<grid, kBlock, 0, st>>>(c, m);
-    });
-  });
-}
-
-// Launch shape of the sliding ring round. The environment overrides are read at each launch, so
-// one process can compare shapes on the same buffers (tools/probe/ring_slide.py); results are
-// identical for every shape. SlideTune and its default are in cfa_slide_shape.h; here u = 0 stands
-// for the tuned width, stepped down where a short row would leave workgroups without a tile
-// (slide_pick_u), and CFA_SLIDE_U = 1, 2 or 4 for exactly that width.
-static_assert(kSlideBlock == kBlock, "cfa_slide_shape.h counts tiles of kBlock lanes");
-static SlideTune slide_tune() {
-  const SlideTune d = kSlideDefault;
-  SlideTune t{env_int("CFA_SLIDE_SEGMENTS", d.segments), env_int("CFA_SLIDE_WG_PER_CU", d.wg_per_cu),
-              env_int("CFA_SLIDE_PF", d.pf), env_int("CFA_SLIDE_SC1", d.sc1) ? 1 : 0, env_int("CFA_SLIDE_U", 0)};
-  if (t.segments <= 0) t.segments = d.segments;
-  if (t.wg_per_cu <= 0) t.wg_per_cu = d.wg_per_cu;
-  if (t.pf < 1 || t.pf > 2) t.pf = d.pf;
-  if (t.u != 1 && t.u != 2 && t.u != 4) t.u = 0;
-  return t;
-}
-template <int HL, int HR, int PF, int U>
-void launch_slide_shape(const SlideArgs& c, long long m, dim3 grid, bool sc1, hipStream_t st) {
-  if (sc1) ring_slide_kernel<HL, HR, PF, U, true><<<grid, kBlock, 0, st>>>(c, m);
-  else ring_slide_kernel<HL, HR, PF, U, false><<<grid, kBlock, 0, st>>>(c, m);
-}
-template <int HL, int HR, int U>
-void launch_slide_u(const SlideArgs& c, long long m, dim3 grid, const SlideTune& t, hipStream_t st) {
-  switch (t.pf) {
-    case 1: launch_slide_shape<HL, HR, 1, U>(c, m, grid, t.sc1, st); break;
-    default: launch_slide_shape<HL, HR, 2, U>(c, m, grid, t.sc1, st); break;
-  }
-}
-template <int HL, int HR>
-void launch_ring_slide(const SlideArgs& sa, long long nvec, hipStream_t st) {
-  const SlideTune t = slide_tune();
-  int segments = t.segments < sa.count ? t.segments : sa.count;
-  if (segments > 65535) segments = 65535;
-  SlideArgs c = sa;
-  c.seg = (sa.count + segments - 1) / segments;
-  const unsigned gy = (unsigned)((sa.count + c.seg - 1) / c.seg);  // no empty segment
-  for_each_chunk(nvec, [&](long long done, long long m) {
-    c.off = done * 4;
-    const int u = t.u ? t.u : slide_pick_u(m, kSlideDefault.u, device_cus(), t.wg_per_cu);
-    // the launch's workgroups over all segments: about wg_per_cu per CU in all
-    const dim3 grid(shared_grid_x(slide_tiles(m, u), t.wg_per_cu, gy), gy);
-    switch (u) {
-      case 4: launch_slide_u<HL, HR, 4>(c, m, grid, t, st); break;
-      case 2: launch_slide_u<HL, HR, 2>(c, m, grid, t, st); break;
-      default: launch_slide_u<HL, HR, 1>(c, m, grid, t, st); break;
-    }
-  });
-}
-
-// The launchers by (hl, hr), each 0..4: the one definition of the 5x5 table.
-#define CFA_HLHR_ROW(F, L) {&F<L, 0>, &F<L, 1>, &F<L, 2>, &F<L, 3>, &F<L, 4>}
-#define CFA_HLHR_TABLE(F) \
-  {CFA_HLHR_ROW(F, 0), CFA_HLHR_ROW(F, 1), CFA_HLHR_ROW(F, 2), CFA_HLHR_ROW(F, 3), CFA_HLHR_ROW(F, 4)}
-void (*const kWindowLaunch[5][5])(const WindowArgs&, long long, hipStream_t) = CFA_HLHR_TABLE(launch_window);
-void (*const kRingLaunch[5][5])(const RingArgs&, long long, hipStream_t) = CFA_HLHR_TABLE(launch_ring_round);
-void (*const kSlideLaunch[5][5])(const SlideArgs&, long long, hipStream_t) = CFA_HLHR_TABLE(launch_ring_slide);
-#undef CFA_HLHR_TABLE
-#undef CFA_HLHR_ROW
-}  // namespace
-
-extern "C" int cfa_mix_window_f32(float* const* out, const float* const* rows, const float* alphas,
-                                  int nb, int hl, int hr, size_t P, void* stream) {
-  if (nb < 1 || nb > kWinMaxDev) return fail(CFA_E_INVALID, "nb %d outside 1..%d", nb, kWinMaxDev);
-  if (hl < 0 || hr < 0 || hl > 4 || hr > 4) return fail(CFA_E_INVALID, "window %d/%d outside 0..4", hl, hr);
-  if (!out || !rows || !alphas) return fail(CFA_E_INVALID, "null table");
-  if (P == 0) return CFA_OK;
-  WindowArgs w{};
-  w.nb = nb;
-  const int nr = nb + hl + hr;
-  bool aligned = true;
-  for (int k = 0; k < nr; ++k) {
-    if (!rows[k]) return fail(CFA_E_INVALID, "null row %d", k);
-    w.rows[k] = rows[k];
-    aligned = aligned && (addr(rows[k]) & 15) == 0;
-  }
-  for (int b = 0; b < nb; ++b) {
-    if (!out[b]) return fail(CFA_E_INVALID, "null output %d", b);
-    for (int k = 0; k < nr; ++k)
-      if (out[b] == rows[k]) return fail(CFA_E_INVALID, "output %d aliases row %d", b, k);
-    w.out[b] = out[b];
-    aligned = aligned && (addr(out[b]) & 15) == 0;
-    w.a[b] = alphas[b];
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const long long nvec = aligned ? (long long)(P / 4) : 0;
-  if (nvec > 0) {
-    kWindowLaunch[hl][hr](w, nvec, st);
-    if (int rc = check_launch("window_vec")) return rc;
-  }
-  const long long begin = nvec * 4;
-  if (begin < (long long)P) {
-    const long long len = (long long)P - begin;
-    window_scalar_kernel<<<grid_for((len + kBlock - 1) / kBlock), kBlock, 0, st>>>(w, hl, hr, begin, (long long)P);
-    if (int rc = check_launch("window_scalar")) return rc;
-  }
-  return CFA_OK;
-}
-
-extern "C" int cfa_mix_ring_round_f32(float* out, const float* in, size_t pitch, const float* alphas, int D,
-                                      int hl, int hr, size_t P, void* stream) {
-  if (D < 1) return fail(CFA_E_INVALID, "device count %d", D);
-  if (hl < 0 || hr < 0 || hl > 4 || hr > 4) return fail(CFA_E_INVALID, "window %d/%d outside 0..4", hl, hr);
-  if (hl + hr >= D) return fail(CFA_E_INVALID, "window %d/%d wider than %d devices", hl, hr, D);
-  if (!out || !in || !alphas) return fail(CFA_E_INVALID, "null buffer");
-  if (pitch < P) return fail(CFA_E_INVALID, "pitch %zu below P %zu", pitch, P);
-  if (P == 0) return CFA_OK;
-  if ((addr(out) & 15) || (addr(in) & 15) || (pitch % 4) || (P % 4))
-    return fail(CFA_E_UNSUPPORTED, "ring round needs 16-byte aligned rows (pitch and P multiples of 4)");
-  const long long outb = (long long)addr(out), inb = (long long)addr(in), span = (long long)D * (long long)pitch * 4;
-  if (outb < inb + span && inb < outb + span) return fail(CFA_E_INVALID, "out overlaps in");
-  if ((long long)(D + kWinMaxDev - 1) / kWinMaxDev > 65535) return fail(CFA_E_INVALID, "D=%d exceeds grid.y", D);
-  RingArgs ra{in, out, alphas, (long long)pitch, 0, D};
-  kRingLaunch[hl][hr](ra, (long long)(P / 4), (hipStream_t)stream);
-  return check_launch("ring_round");
-}
-
-extern "C" int cfa_mix_ring_slide_f32(float* out, size_t out_pitch, const float* in, size_t in_pitch,
-                                      const float* alphas, int rows, int first, int count, int hl, int hr,
-                                      size_t P, void* stream) {
-  if (!out || !in || !alphas) return fail(CFA_E_INVALID, "null buffer");
-  if (rows < 1 || count < 1) return fail(CFA_E_INVALID, "rows %d / count %d below 1", rows, count);
-  if (first < 0 || first >= rows || count > rows || (count != rows && first > rows - count))
-    return fail(CFA_E_INVALID, "devices %d..%d outside a ring of %d rows", first, first + count - 1, rows);
-  if (hl < 0 || hr < 0 || hl > 4 || hr > 4) return fail(CFA_E_INVALID, "window %d/%d outside 0..4", hl, hr);
-  if (hl + hr >= rows) return fail(CFA_E_INVALID, "window %d/%d wider than %d rows", hl, hr, rows);
-  if (in_pitch < P || out_pitch < P)
-    return fail(CFA_E_INVALID, "pitch %zu/%zu below P %zu", out_pitch, in_pitch, P);
-  if (P == 0) return CFA_OK;
-  const unsigned long long outb = addr(out), inb = addr(in);
-  const unsigned long long out_span = ((unsigned long long)(rows - 1) * out_pitch + P) * 4;
-  const unsigned long long in_span = ((unsigned long long)(rows - 1) * in_pitch + P) * 4;
-  if (outb < inb + in_span && inb < outb + out_span) return fail(CFA_E_INVALID, "out overlaps in");
-  if ((outb & 15) || (inb & 15) || (out_pitch % 4) || (in_pitch % 4) || (P % 4))
-    return fail(CFA_E_UNSUPPORTED, "ring slide needs 16-byte aligned rows (pitches and P multiples of 4)");
-  SlideArgs sa{in, out, alphas, (long long)in_pitch, (long long)out_pitch, 0, rows, first, count, count};
-  kSlideLaunch[hl][hr](sa, (long long)(P / 4), (hipStream_t)stream);
-  return check_launch("ring_slide");
-}
-
-// A scheduled entry's own arguments, checked before anything else; sc.sched == nullptr below
-// stands for the static entry points' one table.
-static int sched_args(const int32_t* sched, int S, int T, unsigned long long* round, SchedArgs& sc) {
-  if (S <= 0 || T <= 0) return fail(CFA_E_INVALID, "schedule of %d slots over %d tables", S, T);
-  if (!sched || !round) return fail(CFA_E_INVALID, "null schedule or round counter");
-  sc = SchedArgs{sched, round, (unsigned)S};
-  return CFA_OK;
-}
 // The round is over: the next launch on the stream reads the counter one higher.
 int advance_counter(unsigned long long* counter, hipStream_t st) {
   round_advance_kernel<<<1, 1, 0, st>>>(counter);
   return check_launch("round_advance");
 }
-static int advance_round(const SchedArgs& sc, hipStream_t st) { return advance_counter(sc.round, st); }
+
+// The common part of the CSR round entries: the shared argument checks, the grid from the
+// kernel's tile of kBlock * tile_vec float4, the launch of `fixed`, or under a schedule
+// (sc.sched) of `sched` and then the counter's advance. `own` is the result of the entry's own
+// checks: a failure there is reported after a negative D and before an empty population returns
+// CFA_OK (a negative D's message replaces the one `own` left). launch(kernel, grid, st, nvec)
+// starts the kernel with the entry's arguments; both instances take the same ones.
+template <typename K, typename Coef, typename Launch>
+static int launch_population(K fixed, K sched, const char* name, const char* sched_name, int tile_vec,
+                             float* const* out_ptrs, const float* const* src_ptrs, const int32_t* csr_ptr,
+                             const int32_t* csr_idx, const Coef* csr_coef, const SchedArgs& sc, int D, int own,
+                             size_t P, void* stream, Launch&& launch) {
+  if (D < 0) return fail(CFA_E_INVALID, "negative device count");
+  if (own) return own;
+  if (D == 0 || P == 0) return CFA_OK;
+  if (!out_ptrs || !src_ptrs || !csr_ptr || !csr_idx || !csr_coef)
+    return fail(CFA_E_INVALID, "null population table");
+  if (D > 65535) return fail(CFA_E_INVALID, "D=%d exceeds grid.y limit", D);
+  // Buckets in a population are expected 16-byte aligned (allocator contract, checked by the
+  // host layer); the body runs on float4, the <4-element tail in the first tile column.
+  const long long nvec = (long long)P / 4, tile = (long long)kBlock * tile_vec;
+  const dim3 grid(shared_grid_x((nvec + tile - 1) / tile, pop_wg_per_cu(), D), (unsigned)D);
+  hipStream_t st = (hipStream_t)stream;
+  launch(sc.sched ? sched : fixed, grid, st, nvec);
+  if (int rc = check_launch(sc.sched ? sched_name : name)) return rc;
+  return sc.sched ? advance_round(sc, st) : CFA_OK;
+}
 
 static int population_tf1(float* const* out_ptrs, const float* const* src_ptrs, const int32_t* csr_ptr,
                           const int32_t* csr_idx, const double* csr_coef, const SchedArgs& sc, int D,
                           size_t P, int mode, size_t cbegin, size_t cend, unsigned long long* kept_counts,
                           void* stream) {
-  if (D < 0) return fail(CFA_E_INVALID, "negative device count");
   CompressParams cp{};
-  if (int rc = compress_params(mode, cp)) return rc;
-  if (mode && (!kept_counts || cbegin > cend || cend > P))
-    return fail(CFA_E_INVALID, "compression needs per-device counters and a segment within the bucket");
+  int own = compress_params(mode, cp);
+  if (!own && mode && (!kept_counts || cbegin > cend || cend > P))
+    own = fail(CFA_E_INVALID, "compression needs per-device counters and a segment within the bucket");
   cp.cbegin = (long long)cbegin;
   cp.cend = (long long)cend;
   cp.kept = kept_counts;
-  if (D == 0 || P == 0) return CFA_OK;
-  if (!out_ptrs || !src_ptrs || !csr_ptr || !csr_idx || !csr_coef)
-    return fail(CFA_E_INVALID, "null population table");
-  if (D > 65535) return fail(CFA_E_INVALID, "D=%d exceeds grid.y limit", D);
-  const long long nvec = (long long)P / 4;
-  const unsigned gx = shared_grid_x((nvec + kBlock - 1) / kBlock, pop_wg_per_cu(), D);
-  hipStream_t st = (hipStream_t)stream;
-  if (!sc.sched) {
-    population_tf1_kernel<<<dim3(gx, (unsigned)D), kBlock, 0, st>>>(
-        out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, nvec, (long long)P, cp);
-    return check_launch("population_tf1");
-  }
-  population_tf1_sched_kernel<<<dim3(gx, (unsigned)D), kBlock, 0, st>>>(
-      out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, sc, nvec, (long long)P, cp);
-  if (int rc = check_launch("population_tf1_sched")) return rc;
-  return advance_round(sc, st);
+  return launch_population(population_tf1_kernel<false>, population_tf1_kernel<true>, "population_tf1",
+                           "population_tf1_sched", 1, out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, sc, D, own, P,
+                           stream, [&](auto kernel, dim3 grid, hipStream_t st, long long nvec) {
+                             kernel<<<grid, kBlock, 0, st>>>(out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, sc, nvec,
+                                                             (long long)P, cp);
+                           });
 }
 
 extern "C" int cfa_mix_population_tf1_f32(float* const* out_ptrs, const float* const* src_ptrs,
@@ -758,35 +302,16 @@ extern "C" int cfa_mix_population_sched_tf1_f32(float* const* out_ptrs, const fl
 static int population_f32(float* const* out_ptrs, const float* const* src_ptrs, const int32_t* csr_ptr,
                           const int32_t* csr_idx, const float* csr_coef, const SchedArgs& sc, int D, int rule,
                           size_t P, void* stream) {
-  if (D < 0) return fail(CFA_E_INVALID, "negative device count");
-  if (rule != CFA_RULE_SEQUENTIAL && rule != CFA_RULE_LINEAR)
-    return fail(CFA_E_INVALID, "unknown rule %d", rule);
-  if (D == 0 || P == 0) return CFA_OK;
-  if (!out_ptrs || !src_ptrs || !csr_ptr || !csr_idx || !csr_coef)
-    return fail(CFA_E_INVALID, "null population table");
-  if (D > 65535) return fail(CFA_E_INVALID, "D=%d exceeds grid.y limit", D);
-  hipStream_t st = (hipStream_t)stream;
-  // Buckets in a population are expected 16-byte aligned (allocator contract, checked by the
-  // host layer); the body runs on float4, the <4-element tail in the first tile column.
-  const long long nvec = (long long)P / 4;
-  dim3 grid(shared_grid_x((nvec + 2LL * kBlock - 1) / (2LL * kBlock), pop_wg_per_cu(), D), (unsigned)D);
-  if (!sc.sched) {
-    if (rule == CFA_RULE_SEQUENTIAL)
-      population_kernel<CFA_RULE_SEQUENTIAL><<<grid, kBlock, 0, st>>>(out_ptrs, src_ptrs, csr_ptr,
-                                                                      csr_idx, csr_coef, nvec, (long long)P);
-    else
-      population_kernel<CFA_RULE_LINEAR><<<grid, kBlock, 0, st>>>(out_ptrs, src_ptrs, csr_ptr,
-                                                                  csr_idx, csr_coef, nvec, (long long)P);
-    return check_launch("population");
-  }
-  if (rule == CFA_RULE_SEQUENTIAL)
-    population_sched_kernel<CFA_RULE_SEQUENTIAL><<<grid, kBlock, 0, st>>>(out_ptrs, src_ptrs, csr_ptr, csr_idx,
-                                                                          csr_coef, sc, nvec, (long long)P);
-  else
-    population_sched_kernel<CFA_RULE_LINEAR><<<grid, kBlock, 0, st>>>(out_ptrs, src_ptrs, csr_ptr, csr_idx,
-                                                                      csr_coef, sc, nvec, (long long)P);
-  if (int rc = check_launch("population_sched")) return rc;
-  return advance_round(sc, st);
+  int own = CFA_OK;
+  if (rule != CFA_RULE_SEQUENTIAL && rule != CFA_RULE_LINEAR) own = fail(CFA_E_INVALID, "unknown rule %d", rule);
+  const bool lin = rule == CFA_RULE_LINEAR;
+  return launch_population(lin ? population_kernel<CFA_RULE_LINEAR, false> : population_kernel<CFA_RULE_SEQUENTIAL, false>,
+                           lin ? population_kernel<CFA_RULE_LINEAR, true> : population_kernel<CFA_RULE_SEQUENTIAL, true>,
+                           "population", "population_sched", 2, out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, sc, D,
+                           own, P, stream, [&](auto kernel, dim3 grid, hipStream_t st, long long nvec) {
+                             kernel<<<grid, kBlock, 0, st>>>(out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, sc, nvec,
+                                                             (long long)P);
+                           });
 }
 
 extern "C" int cfa_mix_population_f32(float* const* out_ptrs, const float* const* src_ptrs,
@@ -820,271 +345,23 @@ extern "C" int cfa_mix_population_ended_f32(float* const* out_ptrs, const float*
   SchedArgs sc{};
   if (sched || round)
     if (int rc = sched_args(sched, S, T, round, sc)) return rc;
-  if (D < 0) return fail(CFA_E_INVALID, "negative device count");
+  int own = CFA_OK;
   if (ended_rule != CFA_ENDED_COPY && ended_rule != CFA_ENDED_TRUNCATE && ended_rule != CFA_ENDED_TRUNCATE_EPS)
-    return fail(CFA_E_INVALID, "unknown ended rule %d", ended_rule);
-  if (!ended) return fail(CFA_E_INVALID, "null ended flags");
+    own = fail(CFA_E_INVALID, "unknown ended rule %d", ended_rule);
+  else if (!ended)
+    own = fail(CFA_E_INVALID, "null ended flags");
   // every workgroup of the round reads `ended` while one lane per device writes the other two
-  if (flags_overlap(ended, ended_next, D > 0 ? D : 1) || flags_overlap(ended, saw, D > 0 ? D : 1))
-    return fail(CFA_E_INVALID, "ended_next or saw aliases ended");
-  if (D == 0 || P == 0) return CFA_OK;
-  if (!out_ptrs || !src_ptrs || !csr_ptr || !csr_idx || !csr_coef)
-    return fail(CFA_E_INVALID, "null population table");
-  if (D > 65535) return fail(CFA_E_INVALID, "D=%d exceeds grid.y limit", D);
-  hipStream_t st = (hipStream_t)stream;
-  const EndedArgs ea{ended, ended_next, saw, ended_rule};
-  const long long nvec = (long long)P / 4;  // buckets 16-byte aligned, as cfa_mix_population_f32
-  dim3 grid(shared_grid_x((nvec + 2LL * kBlock - 1) / (2LL * kBlock), pop_wg_per_cu(), D), (unsigned)D);
-  if (!sc.sched) {
-    population_ended_kernel<false><<<grid, kBlock, 0, st>>>(out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, sc, ea,
-                                                            nvec, (long long)P);
-    return check_launch("population_ended");
-  }
-  population_ended_kernel<true><<<grid, kBlock, 0, st>>>(out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, sc, ea,
-                                                         nvec, (long long)P);
-  if (int rc = check_launch("population_ended_sched")) return rc;
-  return advance_round(sc, st);
+  else if (flags_overlap(ended, ended_next, D > 0 ? D : 1) || flags_overlap(ended, saw, D > 0 ? D : 1))
+    own = fail(CFA_E_INVALID, "ended_next or saw aliases ended");
+  // buckets 16-byte aligned and the tile of two float4 per lane, as cfa_mix_population_f32
+  return launch_population(population_ended_kernel<false>, population_ended_kernel<true>, "population_ended",
+                           "population_ended_sched", 2, out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, sc, D, own,
+                           P, stream, [&](auto kernel, dim3 grid, hipStream_t st, long long nvec) {
+                             const EndedArgs ea{ended, ended_next, saw, ended_rule};
+                             kernel<<<grid, kBlock, 0, st>>>(out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, sc, ea,
+                                                             nvec, (long long)P);
+                           });
 }
-
-// ------------------------------------------------------------------------------------------
-// FedAvg parameter-server round (cfa_fedavg_population_round_f32): the server's fold of the
-// round's active rows into the global model (parameter_server_v2.py:146-161) and every device's
-// take of the published model (federated_learning_keras_PS_MNIST.py:307-309,
-// learner_consensus.py:151-152) in one launch on a [D, pitch] stack. A lane owns its columns for
-// the whole round: it loads params, streams the active rows and folds them in list order (the
-// chain is sequential in p, the row loads are not: B rows' loads of U float4 each are issued
-// ahead of their folds), writes params, then walks the D rows for the client rule. No other lane
-// reads or writes those elements of params or of any row, so everything is in place. The steps
-// are div_step / seq_step of cfa_internal.h; a lane whose fold produced a subnormal quotient
-// (div4_rn) walks its column again with the IEEE division, re-reading the rows (C is a run-time
-// count: the rows are not kept in registers as fold<N, SEQUENTIAL_DIV> keeps them).
-// ------------------------------------------------------------------------------------------
-namespace {
-
-struct FedAvgArgs {
-  float* models;           // [D, pitch]
-  float* params;           // [P]
-  const int32_t* act_ptr;  // [T + 1] absolute offsets into act_idx
-  const int32_t* act_idx;  // device ids in fold order
-  const float* act_div;    // [T] C of each list
-  const double* act_rdiv;  // [T] RN_64(1 / C)
-  const int32_t* ended;    // [D] flags, or null
-  long long pitch;
-  int D, client;
-  float u, u_c, d_c;
-  double rd_c;
-};
-
-// The round's list [e0, e1), its divisor, and the row of the transfer-learning step (-1: none).
-struct FedAvgRound {
-  int e0, e1, ended_row;
-  float d;
-  double rd;
-};
-
-// One chain of uniform loads (round -> sched -> the list's bounds and divisor), then the scan of
-// the list for its first flagged entry: the workgroup's lanes take one entry each per pass and
-// keep the smallest flagged position. Called by every lane of the workgroup (it synchronises).
-__device__ __forceinline__ FedAvgRound fedavg_round_lookup(const FedAvgArgs& a, const SchedArgs& sc) {
-  const unsigned long long r = *static_cast<const unsigned long long*>(sc.round);
-  const int t = sc.sched[r % sc.S];
-  FedAvgRound fr{a.act_ptr[t], a.act_ptr[t + 1], -1, a.act_div[t], a.act_rdiv[t]};
-  if (a.ended) {
-    __shared__ int first;
-    if (threadIdx.x == 0) first = fr.e1;
-    __syncthreads();
-    for (int e = fr.e0 + (int)threadIdx.x; e < fr.e1; e += kBlock)
-      if (a.ended[a.act_idx[e]]) {
-        atomicMin(&first, e);
-        break;
-      }
-    __syncthreads();
-    if (first < fr.e1) fr.ended_row = a.act_idx[first];
-  }
-  return fr;
-}
-
-// A lane's column element: a float4 (index in float4 units) or, in the scalar tail, a float.
-template <typename T, bool NT>
-__device__ __forceinline__ T ld_col(const float* row, long long i) {
-  if constexpr (std::is_same_v<T, f4>) return ld4<NT>(row, i);
-  else return row[i];
-}
-template <typename T, bool NT>
-__device__ __forceinline__ void st_col(float* row, long long i, T v) {
-  if constexpr (std::is_same_v<T, f4>) st4<NT>(row, i, v);
-  else row[i] = v;
-}
-
-// The server's fold of the list into p (the lane's U elements at i0 + u * kBlock), B rows' loads
-// in flight. The row ids are wave-uniform: scalar registers.
-template <typename T, int U, int B, bool IEEE>
-__device__ __forceinline__ void fedavg_fold(T (&p)[U], const FedAvgArgs& a, const FedAvgRound& fr, long long i0,
-                                            bool& subnormal) {
-  for (int e = fr.e0; e < fr.e1; e += B) {
-    T x[B][U];
-#pragma unroll
-    for (int b = 0; b < B; ++b)
-      if (e + b < fr.e1) {
-        const float* row = a.models + (long long)__builtin_amdgcn_readfirstlane(a.act_idx[e + b]) * a.pitch;
-#pragma unroll
-        for (int u = 0; u < U; ++u) x[b][u] = ld_col<T, true>(row, i0 + (long long)u * kBlock);
-      }
-#pragma unroll
-    for (int b = 0; b < B; ++b)
-      if (e + b < fr.e1) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) p[u] = div_step<IEEE>(p[u], x[b][u], a.u, fr.d, fr.rd, subnormal);
-      }
-  }
-}
-
-// One step of the divisor rule on a float4 with the redo of a subnormal quotient; IEEE on a float.
-template <typename T>
-__device__ __forceinline__ T div_step_exact(T w, T x, float c, float d, double rd) {
-  bool subnormal = false;
-  if constexpr (std::is_same_v<T, f4>) {
-    const T y = div_step<false>(w, x, c, d, rd, subnormal);
-    if (__builtin_expect(!subnormal, 1)) return y;
-  }
-  return div_step<true>(w, x, c, d, rd, subnormal);
-}
-
-// The whole round on the lane's U column elements at i0 + u * kBlock.
-template <typename T, int U, int B, bool NT>
-__device__ __forceinline__ void fedavg_columns(const FedAvgArgs& a, const FedAvgRound& fr, long long i0) {
-  T p[U];
-#pragma unroll
-  for (int u = 0; u < U; ++u) p[u] = ld_col<T, false>(a.params, i0 + (long long)u * kBlock);
-  if (fr.ended_row >= 0) {  // transfer learning: one step on the first ended device, no division
-    const float* row = a.models + (long long)fr.ended_row * a.pitch;
-#pragma unroll
-    for (int u = 0; u < U; ++u) p[u] = seq_step(p[u], ld_col<T, true>(row, i0 + (long long)u * kBlock), a.u);
-  } else if constexpr (std::is_same_v<T, f4>) {
-    T p0[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) p0[u] = p[u];
-    bool subnormal = false;
-    fedavg_fold<T, U, B, false>(p, a, fr, i0, subnormal);
-    // a subnormal quotient may be an exact tie: the column again with the IEEE division
-    if (__builtin_expect(subnormal, 0)) {
-#pragma unroll
-      for (int u = 0; u < U; ++u) p[u] = p0[u];
-      fedavg_fold<T, U, B, true>(p, a, fr, i0, subnormal);
-    }
-  } else {
-    bool unused = false;
-    fedavg_fold<T, U, B, true>(p, a, fr, i0, unused);
-  }
-  if (fr.e1 > fr.e0) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) st_col<T, false>(a.params, i0 + (long long)u * kBlock, p[u]);
-  }
-  if (a.client == CFA_CLIENT_COPY) {
-    float* row = a.models;
-    for (int d = 0; d < a.D; ++d, row += a.pitch) {
-#pragma unroll
-      for (int u = 0; u < U; ++u) st_col<T, NT>(row, i0 + (long long)u * kBlock, p[u]);
-    }
-  } else if (a.client == CFA_CLIENT_MIX) {
-    for (int d0 = 0; d0 < a.D; d0 += B) {
-      float* const row0 = a.models + (long long)d0 * a.pitch;
-      T w[B][U];
-#pragma unroll
-      for (int b = 0; b < B; ++b)
-        if (d0 + b < a.D) {
-#pragma unroll
-          for (int u = 0; u < U; ++u) w[b][u] = ld_col<T, true>(row0 + b * a.pitch, i0 + (long long)u * kBlock);
-        }
-#pragma unroll
-      for (int b = 0; b < B; ++b)
-        if (d0 + b < a.D) {
-#pragma unroll
-          for (int u = 0; u < U; ++u)
-            st_col<T, NT>(row0 + b * a.pitch, i0 + (long long)u * kBlock,
-                          div_step_exact(w[b][u], p[u], a.u_c, a.d_c, a.rd_c));
-        }
-    }
-  }
-}
-
-template <int U, int B, bool NT>
-__global__ __launch_bounds__(kBlock) void fedavg_round_kernel(FedAvgArgs a, SchedArgs sc, long long nvec,
-                                                              long long P) {
-  const FedAvgRound fr = fedavg_round_lookup(a, sc);
-  const TileWalk<U> tw(nvec);
-  for (const long long base : tw.full_tiles()) fedavg_columns<f4, U, B, NT>(a, fr, base);
-  if (tw.owns_partial())
-    for (const long long i : tw.partial_tile()) fedavg_columns<f4, 1, B, NT>(a, fr, i);
-  // the < 4-element tail, in the same launch: the scalar form of the same operations
-  if (blockIdx.x == 0 && nvec * 4 + threadIdx.x < P) fedavg_columns<float, 1, B, false>(a, fr, nvec * 4 + threadIdx.x);
-}
-
-// Launch shape: FedavgTune of cfa_fedavg_shape.h; the environment overrides are read at each
-// launch, so one process can compare shapes on the same buffers (tools/probe/fedavg_round.py);
-// results are identical for every shape.
-static_assert(kFedavgBlock == kBlock, "cfa_fedavg_shape.h counts tiles of kBlock lanes");
-static FedavgTune fedavg_tune() {
-  const FedavgTune d = kFedavgDefault;
-  FedavgTune t{env_int("CFA_FEDAVG_U", d.u), env_int("CFA_FEDAVG_U", d.u_long), env_int("CFA_FEDAVG_BATCH", d.batch),
-               env_int("CFA_FEDAVG_WG_PER_CU", d.wg_per_cu)};
-  if (t.u != 1 && t.u != 2 && t.u != 4) t.u = d.u, t.u_long = d.u_long;
-  if (t.batch != 4 && t.batch != 8) t.batch = d.batch;
-  if (t.wg_per_cu <= 0) t.wg_per_cu = d.wg_per_cu;
-  return t;
-}
-template <int U, int B>
-void launch_fedavg_ub(const FedAvgArgs& a, const SchedArgs& sc, unsigned grid, bool nt, long long nvec, long long P,
-                      hipStream_t st) {
-  if (nt) fedavg_round_kernel<U, B, true><<<grid, kBlock, 0, st>>>(a, sc, nvec, P);
-  else fedavg_round_kernel<U, B, false><<<grid, kBlock, 0, st>>>(a, sc, nvec, P);
-}
-template <int U>
-void launch_fedavg_u(const FedAvgArgs& a, const SchedArgs& sc, const FedavgTune& t, long long nvec, long long P,
-                     hipStream_t st) {
-  const long long tile = (long long)kBlock * U;
-  cfa_launch_t lc = tune();
-  lc.blocks_per_cu = t.wg_per_cu;
-  const unsigned grid = grid_for((nvec + tile - 1) / tile, lc);
-  if (t.batch == 8) launch_fedavg_ub<U, 8>(a, sc, grid, fedavg_nt_store(P), nvec, P, st);
-  else launch_fedavg_ub<U, 4>(a, sc, grid, fedavg_nt_store(P), nvec, P, st);
-}
-
-}  // namespace
-
-extern "C" int cfa_fedavg_population_round_f32(float* models, size_t pitch, float* params,
-                                               const int32_t* act_ptr, const int32_t* act_idx,
-                                               const float* act_div, const double* act_rdiv, float u,
-                                               const int32_t* sched, int S, int T,
-                                               unsigned long long* round, const int32_t* ended,
-                                               int client, float u_c, float d_c, double rd_c, int D,
-                                               size_t P, void* stream) {
-  SchedArgs sc{};
-  if (int rc = sched_args(sched, S, T, round, sc)) return rc;
-  if (D < 0) return fail(CFA_E_INVALID, "negative device count");
-  if (client != CFA_CLIENT_NONE && client != CFA_CLIENT_COPY && client != CFA_CLIENT_MIX)
-    return fail(CFA_E_INVALID, "unknown client rule %d", client);
-  if (client == CFA_CLIENT_MIX && d_c == 0.0f) return fail(CFA_E_INVALID, "client divisor d_c is 0");
-  if (!act_ptr || !act_idx || !act_div || !act_rdiv) return fail(CFA_E_INVALID, "null active table");
-  if (pitch < P) return fail(CFA_E_INVALID, "pitch %zu below P %zu", pitch, P);
-  if (P == 0) return CFA_OK;
-  if (!params || (D > 0 && !models)) return fail(CFA_E_INVALID, "null models or params");
-  if ((addr(models) & 15) || (addr(params) & 15) || (pitch % 4))
-    return fail(CFA_E_UNSUPPORTED, "FedAvg round needs 16-byte aligned rows (bases aligned, pitch a multiple of 4)");
-  const FedAvgArgs a{models, params, act_ptr, act_idx, act_div, act_rdiv, ended, (long long)pitch,
-                     D, client, u, u_c, d_c, rd_c};
-  const FedavgTune t = fedavg_tune();
-  const long long nvec = (long long)P / 4;
-  hipStream_t st = (hipStream_t)stream;
-  switch (fedavg_u((long long)P, t)) {
-    case 4: launch_fedavg_u<4>(a, sc, t, nvec, (long long)P, st); break;
-    case 2: launch_fedavg_u<2>(a, sc, t, nvec, (long long)P, st); break;
-    default: launch_fedavg_u<1>(a, sc, t, nvec, (long long)P, st); break;
-  }
-  if (int rc = check_launch("fedavg_round")) return rc;
-  return advance_round(sc, st);
-}
-
 
 // ------------------------------------------------------------------------------------------
 // CFA-GE population step (cfa_ge_population_step_f32): stage-1 mix and the neighbours' gradient

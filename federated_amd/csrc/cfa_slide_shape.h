@@ -1,5 +1,5 @@
 // cfa_slide_shape.h — host-only launch-shape rules of the sliding ring round
-// (cfa_mix_ring_slide_f32, cfa_population.hip). No HIP in here: tests/native/slide_shape_test.cpp
+// (cfa_mix_ring_slide_f32, cfa_ring.hip). No HIP in here: tests/native/slide_shape_test.cpp
 // builds it with a plain C++ compiler.
 #pragma once
 

@@ -640,6 +640,30 @@ class Engine:
                   float(rho), float(lr1), float(lr2), int(lr_split), int(bool(use_filtered)), int(P), r_ws, r_out,
                   int(r_M), int(r_sp), self.stream_handle(stream))
 
+    @staticmethod
+    def _check_csr(out_ptrs: torch.Tensor, src_ptrs: torch.Tensor, csr_ptr: torch.Tensor, csr_idx: torch.Tensor,
+                   csr_coef: torch.Tensor, coef_dtype, D: int, sched: Optional[torch.Tensor] = None,
+                   round: Optional[torch.Tensor] = None) -> tuple:
+        """The five tables of a CSR round (int64 pointers, int32 CSR, ``coef_dtype`` coefficients)
+        and their sizes: one table of D+1 row offsets, or with ``sched`` and ``round`` the T tables
+        of a schedule (``_check_schedule``). Returns (S, T), (0, 0) without a schedule."""
+        _check_tables(("out_ptrs", out_ptrs, torch.int64), ("src_ptrs", src_ptrs, torch.int64),
+                      ("csr_ptr", csr_ptr, torch.int32), ("csr_idx", csr_idx, torch.int32),
+                      ("csr_coef" if coef_dtype == torch.float32 else "csr_coef64", csr_coef, coef_dtype))
+        if sched is not None:
+            return Engine._check_schedule(csr_ptr, out_ptrs, sched, round, D)
+        if csr_ptr.numel() != D + 1 or out_ptrs.numel() != D:
+            raise ValueError("csr_ptr must have D+1 entries and out_ptrs D entries")
+        return 0, 0
+
+    @staticmethod
+    def _kept_ptr(mode: int, kept: Optional[torch.Tensor], D: int):
+        """The address of a TF1 round's ``kept`` counters (None without them), which a compression
+        ``mode`` needs: an int64 CUDA tensor of D counters."""
+        if mode and (kept is None or not kept.is_cuda or kept.dtype != torch.int64 or kept.numel() != D):
+            raise TypeError("compression needs kept: an int64 CUDA tensor of D counters")
+        return kept.data_ptr() if kept is not None else None
+
     def population_tf1(self, out_ptrs: torch.Tensor, src_ptrs: torch.Tensor, csr_ptr: torch.Tensor,
                        csr_idx: torch.Tensor, csr_coef64: torch.Tensor, D: int, P: int, stream=None,
                        mode: int = 0, cbegin: int = 0, cend: int = 0,
@@ -648,27 +672,17 @@ class Engine:
         fp32 first subtraction, fp64 chain with fp64 coefficients, one rounding to fp32.
         ``mode`` != 0: the compression epilogue on [cbegin, cend) of every device, counts added
         to ``kept`` (int64 CUDA tensor of D zeroed counters)."""
-        _check_tables(("out_ptrs", out_ptrs, torch.int64), ("src_ptrs", src_ptrs, torch.int64),
-                      ("csr_ptr", csr_ptr, torch.int32), ("csr_idx", csr_idx, torch.int32),
-                      ("csr_coef64", csr_coef64, torch.float64))
-        if csr_ptr.numel() != D + 1 or out_ptrs.numel() != D:
-            raise ValueError("csr_ptr must have D+1 entries and out_ptrs D entries")
-        if mode and (kept is None or not kept.is_cuda or kept.dtype != torch.int64 or kept.numel() != D):
-            raise TypeError("compression needs kept: an int64 CUDA tensor of D counters")
+        self._check_csr(out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef64, torch.float64, D)
         _lib.call("cfa_mix_population_tf1_f32", out_ptrs.data_ptr(), src_ptrs.data_ptr(), csr_ptr.data_ptr(),
                   csr_idx.data_ptr(), csr_coef64.data_ptr(), int(D), int(P), int(mode), int(cbegin), int(cend),
-                  kept.data_ptr() if kept is not None else None, self.stream_handle(stream))
+                  self._kept_ptr(mode, kept, D), self.stream_handle(stream))
 
     def population(self, out_ptrs: torch.Tensor, src_ptrs: torch.Tensor, csr_ptr: torch.Tensor,
                    csr_idx: torch.Tensor, csr_coef: torch.Tensor, D: int, rule: int, P: int,
                    stream=None) -> None:
         """One launch mixing D devices; tables are device tensors (int64 pointers, int32 CSR,
         fp32 coefficients). See cfa_mix_population_f32."""
-        _check_tables(("out_ptrs", out_ptrs, torch.int64), ("src_ptrs", src_ptrs, torch.int64),
-                      ("csr_ptr", csr_ptr, torch.int32), ("csr_idx", csr_idx, torch.int32),
-                      ("csr_coef", csr_coef, torch.float32))
-        if csr_ptr.numel() != D + 1 or out_ptrs.numel() != D:
-            raise ValueError("csr_ptr must have D+1 entries and out_ptrs D entries")
+        self._check_csr(out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, torch.float32, D)
         _lib.call("cfa_mix_population_f32", out_ptrs.data_ptr(), src_ptrs.data_ptr(),
                   csr_ptr.data_ptr(), csr_idx.data_ptr(), csr_coef.data_ptr(), int(D), int(rule),
                   int(P), self.stream_handle(stream))
@@ -693,10 +707,7 @@ class Engine:
         """``population`` under a topology schedule (cfa_mix_population_sched_f32): mixes with
         table ``sched[round % S]`` of the T tables in ``csr_ptr`` (absolute offsets into the
         shared ``csr_idx`` / ``csr_coef``) and leaves ``round`` one higher, in stream order."""
-        _check_tables(("out_ptrs", out_ptrs, torch.int64), ("src_ptrs", src_ptrs, torch.int64),
-                      ("csr_ptr", csr_ptr, torch.int32), ("csr_idx", csr_idx, torch.int32),
-                      ("csr_coef", csr_coef, torch.float32))
-        S, T = self._check_schedule(csr_ptr, out_ptrs, sched, round, D)
+        S, T = self._check_csr(out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, torch.float32, D, sched, round)
         _lib.call("cfa_mix_population_sched_f32", out_ptrs.data_ptr(), src_ptrs.data_ptr(), csr_ptr.data_ptr(),
                   csr_idx.data_ptr(), csr_coef.data_ptr(), sched.data_ptr(), S, T, round.data_ptr(), int(D),
                   int(rule), int(P), self.stream_handle(stream))
@@ -707,15 +718,10 @@ class Engine:
                              cend: int = 0, kept: Optional[torch.Tensor] = None) -> None:
         """``population_tf1`` under a topology schedule (cfa_mix_population_sched_tf1_f32); the
         schedule arguments as ``population_sched``, the rest as ``population_tf1``."""
-        _check_tables(("out_ptrs", out_ptrs, torch.int64), ("src_ptrs", src_ptrs, torch.int64),
-                      ("csr_ptr", csr_ptr, torch.int32), ("csr_idx", csr_idx, torch.int32),
-                      ("csr_coef64", csr_coef64, torch.float64))
-        S, T = self._check_schedule(csr_ptr, out_ptrs, sched, round, D)
-        if mode and (kept is None or not kept.is_cuda or kept.dtype != torch.int64 or kept.numel() != D):
-            raise TypeError("compression needs kept: an int64 CUDA tensor of D counters")
+        S, T = self._check_csr(out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef64, torch.float64, D, sched, round)
         _lib.call("cfa_mix_population_sched_tf1_f32", out_ptrs.data_ptr(), src_ptrs.data_ptr(), csr_ptr.data_ptr(),
                   csr_idx.data_ptr(), csr_coef64.data_ptr(), sched.data_ptr(), S, T, round.data_ptr(), int(D),
-                  int(P), int(mode), int(cbegin), int(cend), kept.data_ptr() if kept is not None else None,
+                  int(P), int(mode), int(cbegin), int(cend), self._kept_ptr(mode, kept, D),
                   self.stream_handle(stream))
 
     def population_ended(self, out_ptrs: torch.Tensor, src_ptrs: torch.Tensor, csr_ptr: torch.Tensor,
@@ -729,22 +735,14 @@ class Engine:
         CUDA tensors of D entries or None, written by the launch. ``ended_rule``:
         _lib.ENDED_COPY / ENDED_TRUNCATE / ENDED_TRUNCATE_EPS. With ``sched`` and ``round`` the
         tables and the counter are those of ``population_sched``; with neither, one table."""
-        _check_tables(("out_ptrs", out_ptrs, torch.int64), ("src_ptrs", src_ptrs, torch.int64),
-                      ("csr_ptr", csr_ptr, torch.int32), ("csr_idx", csr_idx, torch.int32),
-                      ("csr_coef", csr_coef, torch.float32), ("ended", ended, torch.int32))
+        if (sched is None) != (round is None):
+            raise ValueError("sched and round are given together or not at all")
+        S, T = self._check_csr(out_ptrs, src_ptrs, csr_ptr, csr_idx, csr_coef, torch.float32, D, sched, round)
         for name, t in (("ended", ended), ("ended_next", ended_next), ("saw", saw)):
             if t is not None:
                 _check_tables((name, t, torch.int32))
                 if t.numel() != D:
                     raise ValueError(f"{name} must hold one int32 flag per device")
-        if (sched is None) != (round is None):
-            raise ValueError("sched and round are given together or not at all")
-        if sched is None:
-            if csr_ptr.numel() != D + 1 or out_ptrs.numel() != D:
-                raise ValueError("csr_ptr must have D+1 entries and out_ptrs D entries")
-            S = T = 0
-        else:
-            S, T = self._check_schedule(csr_ptr, out_ptrs, sched, round, D)
         _lib.call("cfa_mix_population_ended_f32", out_ptrs.data_ptr(), src_ptrs.data_ptr(), csr_ptr.data_ptr(),
                   csr_idx.data_ptr(), csr_coef.data_ptr(), sched.data_ptr() if sched is not None else None, S, T,
                   round.data_ptr() if round is not None else None, ended.data_ptr(),

@@ -194,6 +194,18 @@ def _zero_on(t: torch.Tensor, stream) -> None:
         t.zero_()
 
 
+def _mix_tf1(engine: Engine, dst, src, tables, sched, compress, kept, D: int, P: int, stream) -> None:
+    """One TF1 population round: ``compress`` = (mode, cbegin, cend), ``kept`` zeroed ahead of a
+    compressing launch, under the schedule ``sched`` = (sched, round) or, with None, one table."""
+    mode, cb, ce = compress
+    if mode:
+        _zero_on(kept, stream)
+    if sched is not None:
+        engine.population_sched_tf1(dst, src, *tables, *sched, D, P, stream, mode, cb, ce, kept if mode else None)
+    else:
+        engine.population_tf1(dst, src, *tables, D, P, stream, mode, cb, ce, kept if mode else None)
+
+
 class _RoundCounter:
     """The round counter of a scheduled population: one device word that the scheduled kernels
     read (round r mixes with table sched[r % S]) and advance, so it needs no host between rounds.
@@ -415,15 +427,11 @@ class PopulationRound(_RoundCounter):
                                          self._flags[cur ^ 1] if propagate else None, self._flags[2], code, D, P,
                                          *(self._sched or (None, None)), stream)
             return
+        if self._tf1:  # never a window round (set_topology)
+            _mix_tf1(self.engine, dst, src, self.tables, self._sched, self._compress, self.kept, D, P, stream)
+            return
         if self._sched is not None:
-            if self._tf1:
-                mode, cb, ce = self._compress
-                if mode:
-                    _zero_on(self.kept, stream)
-                self.engine.population_sched_tf1(dst, src, *self.tables, *self._sched, D, P, stream, mode, cb, ce,
-                                                 self.kept if mode else None)
-            else:
-                self.engine.population_sched(dst, src, *self.tables, *self._sched, D, RULE_SEQUENTIAL, P, stream)
+            self.engine.population_sched(dst, src, *self.tables, *self._sched, D, RULE_SEQUENTIAL, P, stream)
             return
         if self.window is not None:
             hl, hr, alphas = self.window
@@ -434,12 +442,6 @@ class PopulationRound(_RoundCounter):
                 devs = list(range(s, min(s + 8, D)))
                 rows = [models[(s + o) % D] for o in range(-hl, len(devs) + hr)]
                 self.engine.mix_window([out[d] for d in devs], rows, [alphas[d] for d in devs], hl, hr, stream)
-            return
-        if self._tf1:
-            mode, cb, ce = self._compress
-            if mode:
-                _zero_on(self.kept, stream)
-            self.engine.population_tf1(dst, src, *self.tables, D, P, stream, mode, cb, ce, self.kept if mode else None)
             return
         self.engine.population(dst, src, *self.tables, D, RULE_SEQUENTIAL, P, stream)
 
@@ -565,15 +567,7 @@ class Tf1PopulationRound(_RoundCounter, LocalTrainingHooks):
         if self._csr is None:
             raise RuntimeError("set_topology() or set_schedule() first")
         src, dst = self._tables[self._rot]
-        mode, cb, ce = self._compress
-        if mode:
-            _zero_on(self.kept, stream)
-        if self._sched is not None:
-            self.engine.population_sched_tf1(dst, src, *self._csr, *self._sched, self.D, self.P, stream, mode, cb, ce,
-                                             self.kept if mode else None)
-        else:
-            self.engine.population_tf1(dst, src, *self._csr, self.D, self.P, stream, mode, cb, ce,
-                                       self.kept if mode else None)
+        _mix_tf1(self.engine, dst, src, self._csr, self._sched, self._compress, self.kept, self.D, self.P, stream)
         self._rot = (self._rot + 2) % 3  # (current, previous, out) <- (out, current, previous)
 
     # local training between rounds (``set_local_training``, ``epoch``, ``epochs``): the devices train

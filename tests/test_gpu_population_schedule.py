@@ -131,6 +131,32 @@ def test_population_graph_replay_equals_eager(gpu):
     assert graph.round_index == R + R2
 
 
+def test_scheduled_linear_rule_equals_static_linear_rounds(gpu):
+    """``PopulationRound`` only passes the sequential rule, so the scheduled kernel's linear
+    instance is reached through ``Engine.population_sched`` itself: every round equals the static
+    linear kernel (checked against numpy in test_gpu_population.py) on that round's one table,
+    and the counter, which wraps the 9-slot schedule, ends at the number of rounds."""
+    from federated_amd import _lib
+    from federated_amd import topology as T
+    upload = lambda arrays: tuple(torch.from_numpy(a).cuda() for a in arrays)
+    pointers = lambda m: torch.tensor([m[d].data_ptr() for d in range(D)], dtype=torch.int64, device="cuda")
+    tables = upload(T.schedule_csr(_tables(), T.alphas_tf2, D))
+    sched = torch.tensor(SCHED, dtype=torch.int32, device="cuda")
+    counter = torch.zeros(1, dtype=torch.int64, device="cuda")
+    models = torch.tensor(_start("fp32"), device="cuda")
+    got, want = torch.empty_like(models), torch.empty_like(models)
+    src, dst_got, dst_want = pointers(models), pointers(got), pointers(want)
+    R = len(SCHED) + 2
+    for r in range(R):
+        gpu.population_sched(dst_got, src, *tables, sched, counter, D, _lib.RULE_LINEAR, P_FP32)
+        one = upload(T.csr(_tables()[SCHED[r % len(SCHED)]], T.alphas_tf2, D))
+        gpu.population(dst_want, src, *one, D, _lib.RULE_LINEAR, P_FP32)
+        assert torch.equal(got, want), r
+        assert not torch.equal(got, models), r  # the round mixed something
+        models.copy_(got)
+    assert int(counter.item()) == R
+
+
 def _tf1_inputs():
     g = torch.Generator(device="cuda").manual_seed(53)
     return (torch.randn(D, P_TF1, device="cuda", generator=g) * 1e-4,
