@@ -36,6 +36,7 @@ RULE_ACCUMULATE = 3
 
 CLIENT_NONE, CLIENT_COPY, CLIENT_MIX = 0, 1, 2  # cfa_fedavg_population_round_f32 client rules
 ENDED_COPY, ENDED_TRUNCATE, ENDED_TRUNCATE_EPS = 0, 1, 2  # cfa_mix_population_ended_f32 rules
+OPTIM_SGD, OPTIM_MOMENTUM, OPTIM_ADAM = 0, 1, 2  # cfa_optim_step_f32 rules
 
 COMPRESS_NONE = 0
 COMPRESS_SPARSE = 1
@@ -139,6 +140,12 @@ SIGNATURES = {
     "cfa_local_sgd_2nn_f32": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_size_t,
                                        _c_int, _c_int, _c_int, _c_int, ctypes.c_float, _c_int, _c_void_p, _c_void_p,
                                        _c_int, _c_void_p, _c_void_p]),
+    "cfa_optim_tile": (_c_int, []),
+    "cfa_optim_workspace_bytes": (_c_size_t, [_c_int, _c_size_t, _c_int]),
+    "cfa_optim_step_f32": (_c_int, [_c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t,
+                                    _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int,
+                                    ctypes.c_float, ctypes.c_float, ctypes.c_double, ctypes.c_double, ctypes.c_float,
+                                    ctypes.c_float, _c_void_p, _c_size_t, _c_int, _c_size_t, _c_void_p]),
     "cfa_ge_population_step_f32": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                             _c_void_p, _c_int, ctypes.c_double, ctypes.c_float, ctypes.c_float,
                                             _c_size_t, _c_int, _c_size_t, _c_void_p, _c_void_p, _c_int, _c_int,

@@ -553,6 +553,77 @@ class Engine:
             raise ValueError("ml_model must be 1 (CNN) or 2 (2NN)")
         return models
 
+    # -- local optimizer step of a TF2 population ---------------------------------------------
+    def optim_tile(self) -> int:
+        """Elements of a tile of the optimizer step (cfa_optim_tile)."""
+        return int(_lib.load().cfa_optim_tile())
+
+    def optim_workspace(self, D: int, P: int, n_layers: int) -> torch.Tensor:
+        """Workspace of the Adam clip's partial sums (cfa_optim_workspace_bytes)."""
+        n = int(_lib.load().cfa_optim_workspace_bytes(int(D), int(P), int(n_layers)))
+        return torch.empty(max(n // 8, 1), dtype=torch.float64, device=self.device)
+
+    def optim_step(self, rule: int, models: torch.Tensor, grads: torch.Tensor, layer_ptr: torch.Tensor,
+                   trainable: torch.Tensor, t: torch.Tensor, lr: float, m: Optional[torch.Tensor] = None,
+                   v: Optional[torch.Tensor] = None, pow: Optional[torch.Tensor] = None,
+                   skip: Optional[torch.Tensor] = None, momentum: float = 0.0, beta_1: float = 0.9,
+                   beta_2: float = 0.999, epsilon: float = 1e-7, clipnorm: float = 0.0,
+                   workspace: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+        """cfa_optim_step_f32: one local optimizer step of every device of ``models`` [D, P], in
+        place, with the gradients ``grads`` [D, P] (both fp32 CUDA, unit element stride, any row
+        pitch). ``rule``: _lib.OPTIM_SGD (w - lr * g), OPTIM_MOMENTUM (Keras momentum, the
+        accumulator in ``m``) or OPTIM_ADAM (Keras Adam on ``m`` / ``v``, after tf.clip_by_norm per
+        device and layer when ``clipnorm`` > 0, which needs ``workspace`` from
+        ``optim_workspace``). ``layer_ptr`` [n + 1] and ``trainable`` [n] are int32 CUDA tables (a
+        layer with 0 is not touched; the caller checks the table before the upload), ``skip`` [D]
+        int32 CUDA flags or None (a flagged device is not touched), ``t`` [D] int64 CUDA step
+        counters and ``pow`` [D, 2] fp64 CUDA running powers of the betas (Adam), both left one
+        step on for every device stepped, in stream order. ``m`` / ``v`` [D, P] are the caller's
+        state, pitched like ``models``. The library validates the rest (CFAError)."""
+        D, P = _check_nd(models, "models", pitched=True)
+        if _check_nd(grads, "grads", pitched=True) != (D, P):
+            raise ValueError("grads must be [D, P] like models")
+        need = {_lib.OPTIM_SGD: (), _lib.OPTIM_MOMENTUM: ("m",), _lib.OPTIM_ADAM: ("m", "v")}.get(int(rule))
+        if need is None:
+            raise ValueError(f"unknown optimizer rule {rule}")
+        state = {"m": m, "v": v}
+        spitch = P
+        for name in need:
+            s = state[name]
+            if s is None or _check_nd(s, name, pitched=True) != (D, P):
+                raise ValueError(f"{name} must be a [D, P] fp32 CUDA tensor for this rule")
+        if len(need) == 2 and D > 1 and m.stride(0) != v.stride(0):
+            raise ValueError("m and v must have the same row pitch")
+        if need and D > 1:
+            spitch = int(m.stride(0))
+        _check_tables(("layer_ptr", layer_ptr, torch.int32), ("trainable", trainable, torch.int32),
+                      ("t", t, torch.int64))
+        n = trainable.numel()
+        if n < 1 or layer_ptr.numel() != n + 1 or t.numel() != D:
+            raise ValueError("layer_ptr must hold n + 1 offsets, trainable n >= 1 flags and t one counter per device")
+        if skip is not None:
+            _check_tables(("skip", skip, torch.int32))
+            if skip.numel() != D:
+                raise ValueError("skip must hold one int32 flag per device")
+        adam = int(rule) == _lib.OPTIM_ADAM
+        if adam:
+            if pow is None:
+                raise ValueError("Adam needs the running powers pow [D, 2]")
+            _check_tables(("pow", pow, torch.float64))
+            if tuple(pow.shape) != (D, 2):
+                raise ValueError("pow must be [D, 2]")
+        ws_ptr, ws_bytes = None, 0
+        if workspace is not None:
+            _check_tables(("workspace", workspace, torch.float64))
+            ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel() * 8
+        _lib.call("cfa_optim_step_f32", models.data_ptr(), int(models.stride(0)) if D > 1 else P, grads.data_ptr(),
+                  int(grads.stride(0)) if D > 1 else P, state["m"].data_ptr() if need else None,
+                  state["v"].data_ptr() if len(need) == 2 else None, spitch, layer_ptr.data_ptr(),
+                  trainable.data_ptr(), n, skip.data_ptr() if skip is not None else None, t.data_ptr(),
+                  pow.data_ptr() if adam else None, int(rule), float(lr), float(momentum), float(beta_1),
+                  float(beta_2), float(epsilon), float(clipnorm), ws_ptr, ws_bytes, D, P, self.stream_handle(stream))
+        return models
+
     # -- population ------------------------------------------------------------------------
     def mix_window(self, outs: Sequence[torch.Tensor], rows: Sequence[torch.Tensor], alphas: Sequence[Sequence[float]],
                    hl: int, hr: int, stream=None) -> None:
@@ -790,7 +861,8 @@ _engines: dict = {}
 
 for _name, _fn in list(vars(Engine).items()):
     if (callable(_fn) and not isinstance(_fn, (staticmethod, classmethod)) and not _name.startswith("_")
-            and _name not in ("empty", "counter", "stream_handle", "grad_workspace", "grad_splits")):
+            and _name not in ("empty", "counter", "stream_handle", "grad_workspace", "grad_splits", "optim_tile",
+                              "optim_workspace")):
         setattr(Engine, _name, _same_device(_fn))
 
 

@@ -150,6 +150,13 @@ enum {
   CFA_ENDED_TRUNCATE_EPS = 2 /* mixes it with eps = 1 / (prefix length + 1)    consensus_v3.py:233 */
 };
 
+/* Update rules of the population optimizer step (cfa_optim_step_f32). */
+enum {
+  CFA_OPTIM_SGD = 0,      /* w <- w - lr * g                                     SGD(learning_rate) */
+  CFA_OPTIM_MOMENTUM = 1, /* a <- momentum * a - lr * g; w <- w + a              SGD(learning_rate, momentum) */
+  CFA_OPTIM_ADAM = 2      /* Keras Adam without amsgrad, tf.clip_by_norm per layer first   Adam(learning_rate, clipnorm) */
+};
+
 CFA_API int cfa_version(void);
 CFA_API const char* cfa_last_error(void);
 
@@ -576,6 +583,54 @@ CFA_API int cfa_local_sgd_2nn_f32(const float* x, const float* y, int Ns, int L,
                                   float* models, size_t pitch, int D, int batch_stride, int batch_rows,
                                   int steps, float lr, int update, double* cost, double* cost_log,
                                   int log_cap, unsigned long long* epoch, void* stream);
+
+/* (TF2 drivers) The local optimizer step between two rounds, for every device of a TF2
+ * population in one call: what optimizer.apply_gradients(zip(grads, model.trainable_variables))
+ * does on each device (federated_learning_keras_consensus_FL_MNIST.py:363-381) with the three
+ * optimizers the drivers construct. The gradients are the caller's.
+ *   models [D, pitch] fp32, stepped in place; grads [D, grad_pitch] fp32, read only; m, v
+ *           [D, state_pitch] fp32, the caller's state (SGD: neither is read and both may be NULL;
+ *           momentum: m is the accumulator, v may be NULL). All DEVICE arrays with unit element
+ *           stride and pitches >= P. A device whose rows all start 16-byte aligned is streamed in
+ *           16-byte vectors, any other element by element, with the same results.
+ *   layer_ptr [n_layers + 1] int32 (DEVICE), 0 = layer_ptr[0] < ... < layer_ptr[n_layers] = P:
+ *           the layers of a row in get_weights() order, boundaries arbitrary. Device memory: not
+ *           checked here, the caller checks the table before the upload (whatever it holds, no
+ *           access leaves a row or the workspace).
+ *   trainable [n_layers] int32 (DEVICE): a layer with 0 is neither read nor written.
+ *   skip    [D] int32 (DEVICE) or NULL: a device with a non-zero flag is not touched at all, its
+ *           model, state, t and pow stay as they are (the populations' training_end flags).
+ *   t       [D] int64 (DEVICE): steps taken by each device, left one higher for every device
+ *           stepped, in stream order.
+ *   pow     [D, 2] fp64 (DEVICE; Adam only): beta_1^t and beta_2^t, 1 at t = 0, multiplied up
+ *           once per step by the call.
+ * rule (every fp32 operation rounded on its own, no contraction):
+ *   CFA_OPTIM_SGD:      w <- w - lr * g
+ *   CFA_OPTIM_MOMENTUM: a <- momentum * a - lr * g; w <- w + a        (a is m; not Nesterov)
+ *   CFA_OPTIM_ADAM:     per device and trainable layer, when clipnorm > 0, s = sum g^2 (fp64, a
+ *       fixed order, no atomics), g' = g * RN_32(clipnorm / max(sqrt(s), clipnorm)) as
+ *       tf.clip_by_norm does (the factor is exactly 1 at or below the norm; an all-zero layer
+ *       stays zero); clipnorm <= 0: g' = g and no norm pass. Then, with t counted from 1,
+ *       lr_t = RN_32(lr * sqrt(1 - beta_2^t) / (1 - beta_1^t)) formed in fp64,
+ *       m <- m + (g' - m) * RN_32(1 - beta_1); v <- v + (g' * g' - v) * RN_32(1 - beta_2);
+ *       w <- w - lr_t * m / (sqrt(v) + epsilon), all fp32.
+ * workspace: the clip's partial sums, at least cfa_optim_workspace_bytes(D, P, n_layers) bytes of
+ * DEVICE memory (NULL without the clip): one fp64 partial per tile of cfa_optim_tile() elements
+ * and layer it meets; tiles are counted from a row's first element. The same inputs give the
+ * same bits on every run. No host read, allocation or attribute call: capture-safe. Two launches
+ * and the counters' (three with the clip), none per layer or per device.
+ * CFA_E_INVALID: an unknown rule, D, P or n_layers < 1, a null array the rule needs, a pitch
+ * below P, beta_1 or beta_2 outside [0, 1), a non-finite lr or momentum, a negative epsilon, a
+ * workspace too small for the clip. CFA_E_UNSUPPORTED: an array that is not aligned to its
+ * element size, P beyond the int32 table, D > 65535. */
+CFA_API int cfa_optim_tile(void);
+CFA_API size_t cfa_optim_workspace_bytes(int D, size_t P, int n_layers);
+CFA_API int cfa_optim_step_f32(float* models, size_t pitch, const float* grads, size_t grad_pitch, float* m,
+                               float* v, size_t state_pitch, const int32_t* layer_ptr,
+                               const int32_t* trainable, int n_layers, const int32_t* skip, long long* t,
+                               double* pow, int rule, float lr, float momentum, double beta_1, double beta_2,
+                               float epsilon, float clipnorm, void* workspace, size_t workspace_bytes, int D,
+                               size_t P, void* stream);
 
 /* (a1-a6 batched) Population round: one launch mixes D devices.
  * For device d, CSR entries e in [csr_ptr[d], csr_ptr[d+1]) list its sources in order; the
