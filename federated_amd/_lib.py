@@ -35,6 +35,7 @@ RULE_SEQUENTIAL_DIV = 2
 RULE_ACCUMULATE = 3
 
 CLIENT_NONE, CLIENT_COPY, CLIENT_MIX = 0, 1, 2  # cfa_fedavg_population_round_f32 client rules
+FA_INIT, FA_ROUND = 0, 1  # cfa_fa_population_round_f32 modes
 ENDED_COPY, ENDED_TRUNCATE, ENDED_TRUNCATE_EPS = 0, 1, 2  # cfa_mix_population_ended_f32 rules
 OPTIM_SGD, OPTIM_MOMENTUM, OPTIM_ADAM = 0, 1, 2  # cfa_optim_step_f32 rules
 
@@ -122,6 +123,9 @@ SIGNATURES = {
                                                  _c_void_p, ctypes.c_float, _c_void_p, _c_int, _c_int, _c_void_p,
                                                  _c_void_p, _c_int, ctypes.c_float, ctypes.c_float, ctypes.c_double,
                                                  _c_int, _c_size_t, _c_void_p]),
+    "cfa_fa_population_round_f32": (_c_int, [_c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_void_p, _c_void_p,
+                                             ctypes.c_double, _c_int, _c_int, _c_size_t, _c_void_p]),
+    "cfa_fa_round_tile": (_c_size_t, [_c_size_t, _c_int]),
     "cfa_ge_grad_cnn_f32": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
                                      _c_void_p, _c_void_p, _c_int, _c_void_p]),
     "cfa_ge_grad_2nn_f32": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p,

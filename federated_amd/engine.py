@@ -855,6 +855,27 @@ class Engine:
                   ended.data_ptr() if ended is not None else None, int(client), float(client_factor), cd,
                   1.0 / cd if cd else 0.0, D, P, self.stream_handle(stream))
 
+    def cfa_fa_round(self, out: torch.Tensor, models: torch.Tensor, server: torch.Tensor, coef: torch.Tensor,
+                     eps2: float, mode: int = _lib.FA_ROUND, stream=None) -> None:
+        """cfa_fa_population_round_f32: one server epoch of the TF1 CFA-FA driver. ``models``
+        [D, P] (fp32 CUDA, unit element stride, any row pitch): the models the devices published,
+        only read; ``out`` [D, P] likewise: every device's model after the epoch (must not overlap
+        ``models``); ``server`` [P] fp64 CUDA: the server model, folded in place; ``coef`` [D] fp64
+        CUDA: ``b_d`` under ``_lib.FA_INIT``, ``eps * b_d`` under ``_lib.FA_ROUND``. The library
+        validates pitches and the overlap (CFAError)."""
+        D, P = _check_nd(models, "models", pitched=True)
+        if _check_nd(out, "out", pitched=True) != (D, P):
+            raise ValueError(f"out must be [{D}, {P}] like models")
+        _check_bucket(server, "server", P, torch.float64)
+        _check_tables(("coef", coef, torch.float64))
+        if coef.numel() != D:
+            raise ValueError("coef must hold one fp64 coefficient per device")
+        if mode not in (_lib.FA_INIT, _lib.FA_ROUND):
+            raise ValueError("mode must be _lib.FA_INIT or _lib.FA_ROUND")
+        _lib.call("cfa_fa_population_round_f32", out.data_ptr(), int(out.stride(0)) if D > 1 else P,
+                  models.data_ptr(), int(models.stride(0)) if D > 1 else P, server.data_ptr(), coef.data_ptr(),
+                  float(eps2), int(mode), D, P, self.stream_handle(stream))
+
 
 _engines: dict = {}
 

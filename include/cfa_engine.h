@@ -142,6 +142,12 @@ enum {
   CFA_CLIENT_MIX = 2   /* every device mixes it in: w <- w + (u_c * (g - w)) / d_c */
 };
 
+/* Modes of the TF1 CFA-FA server epoch (cfa_fa_population_round_f32). */
+enum {
+  CFA_FA_INIT = 0, /* epoch 0: s <- s + b_d * x_d, the devices keep their models */
+  CFA_FA_ROUND = 1 /* later: s <- s + (eps * b_d) * (x_d - s), then W <- W + eps2 * (s - W) */
+};
+
 /* What a device does with the first neighbour that reports training_end
  * (cfa_mix_population_ended_f32). */
 enum {
@@ -759,6 +765,37 @@ CFA_API int cfa_fedavg_population_round_f32(float* models, size_t pitch, float* 
                                             unsigned long long* round, const int32_t* ended,
                                             int client, float u_c, float d_c, double rd_c, int D,
                                             size_t P, void* stream);
+
+/* (f1 batched, TF1) One server-federation epoch of the CFA-FA driver on a device-resident
+ * population, one launch: the server's fold of the D published models into its fp64 model, then
+ * every device's pull toward it (federated_sample_CNN_CFA_FA.py; the per-model host form is
+ * federated_amd.server.cfa_fa_server_init / _round / cfa_fa_client_mix over cfa_fold_f64).
+ *   in   [D, in_pitch] fp32 rows (DEVICE), row d = the model device d trained and published at
+ *        this epoch (cfa.py:146-153 with consensus disabled). Only read.
+ *   out  [D, out_pitch] fp32 rows (DEVICE), row d = device d's model after the epoch. Must not
+ *        overlap `in`. Columns P .. pitch-1 of either stack are never touched.
+ *   s    [P] fp64 (DEVICE), the server model, updated in place.
+ *   coef [D] fp64 (DEVICE): b_d under CFA_FA_INIT, the one fp64 product eps * b_d under
+ *        CFA_FA_ROUND, formed by the caller as the driver forms it.
+ * CFA_FA_INIT (:73-89): for d = 0 .. D-1 in order, s <- s + coef[d] * x_d; out row d = in row d.
+ * CFA_FA_ROUND (:103-110, :130-133, then :280-283): for d in order, s <- s + coef[d] * (x_d - s);
+ * then with that final s every row W = in row d gives out row d = (float)(W + eps2 * (s - W)).
+ * x_d and W are widened exactly; every product and sum is one fp64 operation with its own rounding
+ * (no FMA), the client result is rounded once to fp32: numpy's values bit for bit, identical on
+ * every run and under graph replay (a lane owns its columns; no atomics, no workspace, nothing
+ * queried or allocated at launch).
+ * Rows and s may have any alignment their element types allow: when every base is 16-byte aligned
+ * and both pitches are multiples of 4 the rows go as float4 and s as double2, anything else
+ * element by element with the same results. With D above the load batch (8, or 4 under
+ * CFA_FA_BATCH=4) the D input rows are read twice, once per step; s and coef once.
+ * CFA_E_INVALID: a null pointer, D < 0, a pitch below P, an unknown mode, `out` overlapping `in`.
+ * P == 0: CFA_OK, nothing launched. D == 0: s is left unchanged. */
+CFA_API int cfa_fa_population_round_f32(float* out, size_t out_pitch, const float* in, size_t in_pitch,
+                                        double* s, const double* coef, double eps2, int mode, int D,
+                                        size_t P, void* stream);
+/* Elements of one workgroup's tile of that launch for rows of P elements (aligned: the float4
+ * form; else the element form): where its grid-stride loop and its partial tile begin. */
+CFA_API size_t cfa_fa_round_tile(size_t P, int aligned);
 
 /* (a4 batched) CFA-GE population step: stage 1 and the gradient step of every device of a
  * device-resident population in one launch (cfa_ge_2stage.py:446-466, then :591-621). For device
