@@ -445,7 +445,8 @@ int sgd_args(const char* fn, const float* x, const float* y, int Ns, float* mode
     return fail(CFA_E_INVALID, "%s: minibatch %d ends at row %lld of %d", fn, steps - 1,
                 (long long)(steps - 1) * batch_stride + batch_rows, Ns);
   if ((long long)pitch < P) return fail(CFA_E_INVALID, "%s: pitch %zu below the model's %lld parameters", fn, pitch, P);
-  if (!x || !y || !models) return fail(CFA_E_INVALID, "%s: null buffer", fn);
+  // an empty population has no buffers: D == 0 returns before anything is read
+  if (D > 0 && (!x || !y || !models)) return fail(CFA_E_INVALID, "%s: null buffer", fn);
   if ((cost_log == nullptr) != (epoch == nullptr))
     return fail(CFA_E_INVALID, "%s: cost_log and epoch are given together or not at all", fn);
   if (cost_log && log_cap < 1) return fail(CFA_E_INVALID, "%s: log_cap %d must be >= 1", fn, log_cap);
