@@ -1,5 +1,5 @@
-// cfa_grad_common.h — what the TF1 model-graph kernels share (cfa_grad.hip: the CFA-GE gradient
-// evaluation; cfa_local_sgd.hip: the local SGD epoch): the clip bounds of the cost, TF's SAME
+// cfa_grad_common.h — what the TF1 model-graph kernels share below the graphs themselves
+// (cfa_tf1_graph.h has the graphs' phases and geometry): the clip bounds of the cost, TF's SAME
 // padding, the softmax lane width, the workgroup size, the global -> LDS copy and the dynamic-LDS
 // limit of a kernel. Not installed, not an ABI.
 #pragma once
@@ -15,7 +15,7 @@ __host__ __device__ inline int same_left(int L, int k, int s) {
   return total / 2;
 }
 
-// lanes per sample of softmax_xent_backward: the power of two >= C (C <= 64, checked on the host)
+// lanes per sample of softmax_xent: the power of two >= C (C <= 64, checked on the host)
 inline int softmax_width(int C) {
   int w = 1;
   while (w < C) w <<= 1;

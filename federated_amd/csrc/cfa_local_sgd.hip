@@ -1,22 +1,23 @@
 // cfa_local_sgd.hip — one local epoch of plain minibatch SGD for every device of a TF1 population
 // in ONE launch (tensorflow1_implementations/federated_sample_CNN_CFA-GE.py:137-173 and
 // federated_sample_2NN_CFA.py:97-101: per minibatch W <- W_ext - learning_rate * grad, :114-118,
-// then the validation cost :163-172), on the two model graphs of cfa_grad.hip.
+// then the validation cost :163-172), on the two model graphs of cfa_tf1_graph.h.
 //
 // One workgroup owns one device for the whole launch: its model is read from global memory once,
-// stays in LDS for all `steps` minibatches and is stepped there, and is written back once. The
-// graph of a minibatch is the graph of cfa_grad.hip (same phases, same summation orders); what
-// differs is that the gradient of a parameter is not stored but applied to the LDS copy by the
-// thread that owns it, after every read of the pre-update value (the hidden-layer gradient reads
-// the pre-update W2; a barrier separates it from W2's step). The next minibatch's samples are
-// loaded into registers before the current one's first phase and stored to the other half of a
-// double buffer after its last, so their global round trip hides behind the compute.
+// stays in LDS for all `steps` minibatches and is stepped there, and is written back once. A
+// minibatch runs the phases of cfa_tf1_graph.h, the functions cfa_grad.hip runs, so the gradient
+// is that file's by construction; what differs is that the gradient of a parameter is not stored
+// but applied to the LDS copy by the thread that owns it (SgdSink), after every read of the
+// pre-update value (the hidden-layer gradient reads the pre-update W2; a barrier separates it
+// from W2's step). The next minibatch's samples are loaded into registers before the current
+// one's first phase and stored to the other half of a double buffer after its last, so their
+// global round trip hides behind the compute.
 //
 // update = 0 is the validation pass: forward only, models untouched. The mean minibatch cost of
 // the launch is accumulated in fp64 (the driver's Python float `avg_cost += c / total_batch`).
 // Every output is owned by one thread and every sum runs in a fixed order: a launch is
 // deterministic.
-#include "cfa_grad_common.h"
+#include "cfa_tf1_graph.h"
 
 namespace {
 
@@ -59,36 +60,6 @@ struct Prefetch {
   }
 };
 
-// Softmax and clipped cross-entropy of logits z[nb][C]: cs[b] = -sum_c y_c log(clip(pred_c)), and
-// with `backward` z becomes d cost / d logits in place, as softmax_xent_backward of cfa_grad.hip
-// leaves it (the same operations in the same order). One lane per class, W >= C lanes per sample.
-__device__ void softmax_xent_cost(float* z, const float* y, float* cs, int nb, int C, int W, float invB,
-                                  bool backward, int tid, int T) {
-  for (int idx = tid; idx < nb * W; idx += T) {
-    const int b = idx / W, c = idx % W;
-    const bool valid = c < C;
-    const float zc = valid ? z[b * C + c] : -INFINITY;
-    const float yc = valid ? y[b * C + c] : 0.f;
-    float mx = zc;
-    for (int o = W >> 1; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, W));
-    const float e = valid ? expf(zc - mx) : 0.f;
-    float s = e;
-    for (int o = W >> 1; o > 0; o >>= 1) s += __shfl_xor(s, o, W);
-    const float p = e / s;  // pred
-    const float pc = fminf(fmaxf(p, kClipLo), kClipHi);
-    float l = valid ? yc * logf(pc) : 0.f;
-    for (int o = W >> 1; o > 0; o >>= 1) l += __shfl_xor(l, o, W);
-    if (c == 0) cs[b] = -l;
-    if (backward) {
-      const bool pass = valid && p >= kClipLo && p <= kClipHi;
-      const float dp = pass ? -(yc / pc) * invB : 0.f;
-      float dot = dp * p;
-      for (int o = W >> 1; o > 0; o >>= 1) dot += __shfl_xor(dot, o, W);
-      if (valid) z[b * C + c] = (dp - dot) * p;
-    }
-  }
-}
-
 // Thread 0 after the cost phase's barrier: the minibatch's mean cost in fp32 (reduce_mean), added
 // to the launch's mean in fp64.
 __device__ __forceinline__ void add_cost(double& acc, const float* cs, int nb, int steps) {
@@ -107,13 +78,6 @@ __device__ __forceinline__ void put_cost(const SgdArgs& a, int dv, int D, double
   }
 }
 
-struct CnnGeom {
-  int L, C, F, NC, S;
-  int SW;              // softmax lanes per sample
-  int L1, L2, pl, ql;  // conv / pool output lengths, left pads
-  int P;
-};
-
 // LDS floats of the CNN kernel: the model, two minibatches of samples and labels, and per sample
 // pooled / argmax / d pooled, logits, the conv-gradient partial sums and the cost.
 inline long long cnn_sgd_lds(const CnnGeom& d, int nb) {
@@ -121,11 +85,11 @@ inline long long cnn_sgd_lds(const CnnGeom& d, int nb) {
   return d.P + (long long)nb * (2LL * (d.L + d.C) + 3 * LN + d.C + (long long)d.F * d.NC + d.NC + 1);
 }
 
-// FT, ST as grad_cnn_kernel of cfa_grad.hip: the CFA-GE geometry unrolled, or runtime loops.
+// FT, ST: conv_pool_forward's.
 template <int FT, int ST>
 __global__ __launch_bounds__(kGradBlock) void local_sgd_cnn_kernel(SgdArgs a, CnnGeom d) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int nb = a.nb, LN = d.L2 * d.NC;
+  const int nb = a.nb, LN = d.L2 * d.NC, P = (int)d.P;
   const int nW1 = d.F * d.NC, nW2 = LN * d.C, nG1 = nW1 + d.NC;
   float* W1 = lds;                        // [F][NC]
   float* b1 = W1 + nW1;                   // [NC]
@@ -146,15 +110,15 @@ __global__ __launch_bounds__(kGradBlock) void local_sgd_cnn_kernel(SgdArgs a, Cn
   const float* yd = a.y + (long long)dv * a.Ns * d.C;
   const int nx = nb * d.L, ny = nb * d.C;
   const float invB = 1.0f / (float)nb;
-  const float lr = a.lr;
+  const SgdSink sink{a.lr};
 
   // the first minibatch and the model, all in flight together: one global round trip
   Prefetch pf;
   pf.load(xd, nx, yd, ny, tid, T);
-  stage(W1, m, d.P, tid, T);
+  stage(W1, m, P, tid, T);
   pf.store(xs0, xd, nx, ys0, yd, ny, tid, T);
   __syncthreads();
-  const bool taps_in_regs = d.F <= kMaxTaps && T % d.NC == 0;
+  const bool taps_in_regs = cnn_taps_in_regs(d, T);
   double acc = 0.0;
   for (int i = 0; i < a.steps; ++i) {
     const float* xs = xs0 + (i & 1) * nx;
@@ -164,157 +128,34 @@ __global__ __launch_bounds__(kGradBlock) void local_sgd_cnn_kernel(SgdArgs a, Cn
     const float* xn = xd + (long long)(more ? i + 1 : i) * a.bstride * d.L;
     const float* yn = yd + (long long)(more ? i + 1 : i) * a.bstride * d.C;
     pf.load(xn, more ? nx : 0, yn, more ? ny : 0, tid, T);
-    // the conv taps of this thread's channel (T is a multiple of NC, so every item a thread takes
-    // below has the same channel c = tid % NC), reloaded from the stepped W1
     float wreg[kMaxTaps];
-    {
-      const int creg = tid % d.NC;
-      constexpr int KT = FT > 0 ? FT : kMaxTaps;
-#pragma unroll
-      for (int k = 0; k < kMaxTaps; ++k) wreg[k] = 0.f;
-      if (taps_in_regs) {
-#pragma unroll
-        for (int k = 0; k < KT; ++k)
-          if (FT > 0 || k < d.F) wreg[k] = W1[k * d.NC + creg];
-      }
-    }
-    // conv + bias + relu evaluated inside each pooling window; keep the max and its position
-    for (int idx = tid; idx < nb * LN; idx += T) {
-      const int b = idx / LN, r = idx % LN, q = r / d.NC, c = r % d.NC;
-      const float* xb = xs + b * d.L;
-      float best = -INFINITY;
-      int barg = -1;
-      bool done = false;
-      if constexpr (FT > 0 && ST > 0) {
-        // branch-free: samples outside [0, L) read as 0, positions outside [0, L1) never win
-        constexpr int NX = (ST - 1) * ST + FT;
-        const int p0 = q * ST - d.ql, t0 = p0 * ST - d.pl;
-        if (taps_in_regs) {
-          float xv[NX];
-#pragma unroll
-          for (int u = 0; u < NX; ++u) {
-            const int t = t0 + u;
-            const bool in = t >= 0 && t < d.L;
-            const float v = xb[in ? t : 0];
-            xv[u] = in ? v : 0.f;
-          }
-#pragma unroll
-          for (int j = 0; j < ST; ++j) {
-            float z = 0.f;
-#pragma unroll
-            for (int k = 0; k < FT; ++k) z = fmaf(xv[j * ST + k], wreg[k], z);
-            z += b1[c];
-            const float h = z > 0.f ? z : 0.f;
-            const int p = p0 + j;
-            if (p >= 0 && p < d.L1 && h > best) {
-              best = h;
-              barg = p;
-            }
-          }
-          done = true;
-        }
-      }
-      for (int j = 0; j < d.S && !done; ++j) {
-        const int p = q * d.S - d.ql + j;
-        if (p < 0 || p >= d.L1) continue;
-        const int t0 = p * d.S - d.pl;
-        float z = 0.f;
-        for (int k = 0; k < d.F; ++k) {
-          const int t = t0 + k;
-          if (t >= 0 && t < d.L) z = fmaf(xb[t], W1[k * d.NC + c], z);
-        }
-        z += b1[c];
-        const float h = z > 0.f ? z : 0.f;
-        if (h > best) {
-          best = h;
-          barg = p;
-        }
-      }
-      pooled[idx] = best;
-      arg[idx] = barg;
-    }
+    load_taps<FT>(wreg, W1, d, taps_in_regs, tid);  // reloaded from the stepped W1
+    conv_pool_forward<FT, ST>(pooled, arg, xs, W1, b1, wreg, taps_in_regs, nb, d, tid, T);
     __syncthreads();
-    // logits: 8 lanes per (sample, class), strided partial sums, xor-shuffle reduction
-    for (int idx = tid; idx < nb * d.C * 8; idx += T) {
-      const int o = idx >> 3, lane = idx & 7;
-      const int b = o / d.C, k = o % d.C;
-      float z = 0.f;
-      for (int j = lane; j < LN; j += 8) z = fmaf(pooled[b * LN + j], W2[j * d.C + k], z);
-      z += __shfl_xor(z, 1, 8);
-      z += __shfl_xor(z, 2, 8);
-      z += __shfl_xor(z, 4, 8);
-      if (lane == 0) zl[o] = z + b2[k];
-    }
+    cnn_logits(zl, pooled, W2, b2, nb, LN, d.C, tid, T);
     __syncthreads();
-    softmax_xent_cost(zl, ys, cs, nb, d.C, d.SW, invB, a.update != 0, tid, T);
+    softmax_xent<true>(zl, ys, cs, nb, d.C, d.SW, invB, a.update != 0, tid, T);
     __syncthreads();
     if (tid == 0) add_cost(acc, cs, nb, a.steps);
     if (a.update) {
       // the gradient flowing into the pooled features, through the pre-update W2
-      for (int idx = tid; idx < nb * LN; idx += T) {
-        const int b = idx / LN, j = idx % LN;
-        float s = 0.f;
-        for (int k = 0; k < d.C; ++k) s = fmaf(zl[b * d.C + k], W2[j * d.C + k], s);
-        dfc[idx] = pooled[idx] > 0.f ? s : 0.f;  // relu gradient at the window's max
-      }
+      relu_layer_backward(dfc, pooled, zl, W2, nb, LN, d.C, tid, T);
       __syncthreads();
       // the dense layer's step, each element by the thread that owns it
-      for (int idx = tid; idx < nW2; idx += T) {
-        const int j = idx / d.C, k = idx % d.C;
-        float s = 0.f;
-#pragma unroll 4
-        for (int b = 0; b < nb; ++b) s = fmaf(pooled[b * LN + j], zl[b * d.C + k], s);
-        W2[idx] = W2[idx] - lr * s;
-      }
-      for (int k = tid; k < d.C; k += T) {
-        float s = 0.f;
-        for (int b = 0; b < nb; ++b) s += zl[b * d.C + k];
-        b2[k] = b2[k] - lr * s;
-      }
-      // conv gradients per (weight, sample): only each window's max position receives gradient
-      for (int idx = tid; idx < nG1 * nb; idx += T) {  // e fastest: lanes read neighbouring channels
-        const int e = idx % nG1, b = idx / nG1;
-        float s = 0.f;
-        if (e < nW1) {
-          const int k = e / d.NC, c = e % d.NC;
-#pragma unroll 7
-          for (int q = 0; q < d.L2; ++q) {  // select, not branch: the loads stay in flight together
-            const int f = b * LN + q * d.NC + c;
-            const int t = arg[f] * d.S + k - d.pl;
-            const bool in = t >= 0 && t < d.L;
-            const float xv = xs[b * d.L + (in ? t : 0)];
-            s = fmaf(dfc[f], in ? xv : 0.f, s);
-          }
-        } else {
-          const int c = e - nW1;
-#pragma unroll 7
-          for (int q = 0; q < d.L2; ++q) s += dfc[b * LN + q * d.NC + c];
-        }
-        part[b * nG1 + e] = s;
-      }
+      weight_sums<4>(W2, nW2, d.C, pooled, LN, zl, nb, sink, tid, T);
+      column_sums(b2, d.C, zl, nb, sink, tid, T);
+      conv_grad_partials(part, xs, arg, dfc, nb, d, tid, T);
       __syncthreads();
-      for (int e = tid; e < nG1; e += T) {  // W1 and b1 are contiguous: sum over the samples in order
-        float s = 0.f;
-        for (int b = 0; b < nb; ++b) s += part[b * nG1 + e];
-        W1[e] = W1[e] - lr * s;
-      }
+      column_sums(W1, nG1, part, nb, sink, tid, T);  // W1 and b1 are contiguous
     }
     pf.store(xs0 + ((i + 1) & 1) * nx, xn, more ? nx : 0, ys0 + ((i + 1) & 1) * ny, yn, more ? ny : 0, tid, T);
     __syncthreads();
   }
   if (a.update)
-    for (int j = tid; j < d.P; j += T) m[j] = W1[j];
+    for (int j = tid; j < P; j += T) m[j] = W1[j];
   if (tid == 0) put_cost(a, dv, D, acc);
 }
 
-constexpr int kSpan = 32;  // first-layer inputs per partial sum, as cfa_grad.hip
-
-struct NnGeom {
-  int L, H, C;
-  int SW;  // softmax lanes per sample
-  int G;   // ceil(L / kSpan) slices of the input dimension for the first layer's partial sums
-  int P;
-};
 
 inline long long nn_sgd_lds(const NnGeom& d, int nb) {
   return d.P + (long long)nb * (2LL * (d.L + d.C) + 2LL * d.H + d.C + (long long)d.G * d.H + 1);
@@ -322,7 +163,7 @@ inline long long nn_sgd_lds(const NnGeom& d, int nb) {
 
 __global__ __launch_bounds__(kGradBlock) void local_sgd_2nn_kernel(SgdArgs a, NnGeom d) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int nb = a.nb, nW1 = d.L * d.H;
+  const int nb = a.nb, nW1 = d.L * d.H, P = (int)d.P;
   float* W1 = lds;                     // [L][H]
   float* b1 = W1 + nW1;                // [H]
   float* W2 = b1 + d.H;                // [H][C]
@@ -341,11 +182,11 @@ __global__ __launch_bounds__(kGradBlock) void local_sgd_2nn_kernel(SgdArgs a, Nn
   const float* yd = a.y + (long long)dv * a.Ns * d.C;
   const int nx = nb * d.L, ny = nb * d.C;
   const float invB = 1.0f / (float)nb;
-  const float lr = a.lr;
+  const SgdSink sink{a.lr};
 
   Prefetch pf;
   pf.load(xd, nx, yd, ny, tid, T);
-  stage(W1, m, d.P, tid, T);
+  stage(W1, m, P, tid, T);
   pf.store(xs0, xd, nx, ys0, yd, ny, tid, T);
   __syncthreads();
   double acc = 0.0;
@@ -356,80 +197,38 @@ __global__ __launch_bounds__(kGradBlock) void local_sgd_2nn_kernel(SgdArgs a, Nn
     const float* xn = xd + (long long)(more ? i + 1 : i) * a.bstride * d.L;
     const float* yn = yd + (long long)(more ? i + 1 : i) * a.bstride * d.C;
     pf.load(xn, more ? nx : 0, yn, more ? ny : 0, tid, T);
-    // first layer as G partial sums over kSpan-wide slices of the input dimension; a (slice, h)
-    // pair's weights are read once and serve every sample
+    // a (slice, h) pair's weights are reloaded from the stepped W1 once per minibatch and serve
+    // every sample
     for (int idx = tid; idx < d.G * d.H; idx += T) {
       const int h = idx % d.H, grp = idx / d.H, i0 = grp * kSpan, n = min(kSpan, d.L - i0);
       float w[kSpan];
 #pragma unroll
       for (int u = 0; u < kSpan; ++u) w[u] = W1[(i0 + (u < n ? u : 0)) * d.H + h];
-      for (int b = 0; b < nb; ++b) {
-        const float* xb = xs + b * d.L + i0;
-        float z = 0.f;
-#pragma unroll
-        for (int u = 0; u < kSpan; ++u)
-          if (u < n) z = fmaf(xb[u], w[u], z);
-        zpart[(grp * nb + b) * d.H + h] = z;
-      }
+      nn_slice_partials<false>(zpart, nb, xs, w, grp, h, nb, d);
     }
     __syncthreads();
-    for (int idx = tid; idx < nb * d.H; idx += T) {
-      const int b = idx / d.H, h = idx % d.H;
-      float z = 0.f;
-      for (int grp = 0; grp < d.G; ++grp) z += zpart[(grp * nb + b) * d.H + h];
-      z += b1[h];
-      act[idx] = z > 0.f ? z : 0.f;
-    }
+    hidden_from_partials(act, zpart, nb, b1, nb, d, tid, T);
     __syncthreads();
-    for (int idx = tid; idx < nb * d.C; idx += T) {
-      const int b = idx / d.C, k = idx % d.C;
-      float z = 0.f;
-      for (int h = 0; h < d.H; ++h) z = fmaf(act[b * d.H + h], W2[h * d.C + k], z);
-      zl[idx] = z + b2[k];
-    }
+    nn_logits(zl, act, W2, b2, nb, d, tid, T);
     __syncthreads();
-    softmax_xent_cost(zl, ys, cs, nb, d.C, d.SW, invB, a.update != 0, tid, T);
+    softmax_xent<true>(zl, ys, cs, nb, d.C, d.SW, invB, a.update != 0, tid, T);
     __syncthreads();
     if (tid == 0) add_cost(acc, cs, nb, a.steps);
     if (a.update) {
       // the hidden layer's gradient, through the pre-update W2
-      for (int idx = tid; idx < nb * d.H; idx += T) {
-        const int b = idx / d.H, h = idx % d.H;
-        float s = 0.f;
-        for (int k = 0; k < d.C; ++k) s = fmaf(zl[b * d.C + k], W2[h * d.C + k], s);
-        dz[idx] = act[idx] > 0.f ? s : 0.f;
-      }
+      relu_layer_backward(dz, act, zl, W2, nb, d.H, d.C, tid, T);
       __syncthreads();
       // every parameter's step by the thread that owns it
-      for (int idx = tid; idx < d.H * d.C; idx += T) {
-        const int h = idx / d.C, k = idx % d.C;
-        float s = 0.f;
-        for (int b = 0; b < nb; ++b) s = fmaf(act[b * d.H + h], zl[b * d.C + k], s);
-        W2[idx] = W2[idx] - lr * s;
-      }
-      for (int k = tid; k < d.C; k += T) {
-        float s = 0.f;
-        for (int b = 0; b < nb; ++b) s += zl[b * d.C + k];
-        b2[k] = b2[k] - lr * s;
-      }
-      for (int idx = tid; idx < nW1; idx += T) {  // W1 -= lr * x^T dz
-        const int j = idx / d.H, h = idx % d.H;
-        float s = 0.f;
-#pragma unroll 4
-        for (int b = 0; b < nb; ++b) s = fmaf(xs[b * d.L + j], dz[b * d.H + h], s);
-        W1[idx] = W1[idx] - lr * s;
-      }
-      for (int h = tid; h < d.H; h += T) {
-        float s = 0.f;
-        for (int b = 0; b < nb; ++b) s += dz[b * d.H + h];
-        b1[h] = b1[h] - lr * s;
-      }
+      weight_sums<0>(W2, d.H * d.C, d.C, act, d.H, zl, nb, sink, tid, T);
+      column_sums(b2, d.C, zl, nb, sink, tid, T);
+      weight_sums<4>(W1, nW1, d.H, xs, d.L, dz, nb, sink, tid, T);  // W1 -= lr * x^T dz
+      column_sums(b1, d.H, dz, nb, sink, tid, T);
     }
     pf.store(xs0 + ((i + 1) & 1) * nx, xn, more ? nx : 0, ys0 + ((i + 1) & 1) * ny, yn, more ? ny : 0, tid, T);
     __syncthreads();
   }
   if (a.update)
-    for (int j = tid; j < d.P; j += T) m[j] = W1[j];
+    for (int j = tid; j < P; j += T) m[j] = W1[j];
   if (tid == 0) put_cost(a, dv, D, acc);
 }
 
@@ -455,8 +254,10 @@ int sgd_args(const char* fn, const float* x, const float* y, int Ns, float* mode
   return CFA_OK;
 }
 
-// LDS of a launch: within the default 64 KiB, or the kernel's limit raised to the device's.
-int sgd_lds(const char* fn, const void* kern, long long floats, size_t& bytes) {
+// LDS of a launch: within the default 64 KiB, or the kernel's limit raised to the device's. The
+// kernels index the model's P parameters and the LDS with ints.
+int sgd_lds(const char* fn, const void* kern, long long P, long long floats, size_t& bytes) {
+  if (P > (1 << 20)) return fail(CFA_E_UNSUPPORTED, "%s: a model of %lld parameters does not fit the LDS", fn, P);
   const long long need = 4 * floats, limit = device_lds_max();
   if (need > limit || (need > 65536 && !raise_lds_limit(kern, (int)limit)))
     return fail(CFA_E_UNSUPPORTED, "%s: model, two minibatches and activations need %lld bytes of LDS", fn, need);
@@ -489,29 +290,17 @@ extern "C" int cfa_local_sgd_cnn_f32(const float* x, const float* y, int Ns, int
                                      double* cost, double* cost_log, int log_cap, unsigned long long* epoch,
                                      void* stream) {
   const char* fn = "cfa_local_sgd_cnn_f32";
-  if (L < 1 || classes < 1 || filter < 1 || number < 1 || stride < 1)
-    return fail(CFA_E_INVALID, "%s: bad dimensions (L %d C %d F %d NC %d S %d)", fn, L, classes, filter, number,
-                stride);
   CnnGeom d;
-  d.L = L, d.C = classes, d.F = filter, d.NC = number, d.S = stride;
-  d.L1 = (L + stride - 1) / stride;
-  d.L2 = (d.L1 + stride - 1) / stride;
-  d.pl = same_left(L, filter, stride);
-  d.ql = same_left(d.L1, stride, stride);
-  const long long P = (long long)filter * number + number + (long long)d.L2 * number * classes + classes;
+  if (int rc = cnn_geom(fn, L, classes, filter, number, stride, d)) return rc;
   SgdArgs a;
   if (int rc = sgd_args(fn, x, y, Ns, models, pitch, D, batch_stride, batch_rows, steps, lr, update, cost, cost_log,
-                        log_cap, epoch, P, a))
+                        log_cap, epoch, d.P, a))
     return rc;
   if (D == 0) return CFA_OK;
-  if (classes > 64) return fail(CFA_E_UNSUPPORTED, "%s: more than 64 classes", fn);
-  if (P > (1 << 20)) return fail(CFA_E_UNSUPPORTED, "%s: a model of %lld parameters does not fit the LDS", fn, P);
-  d.P = (int)P;
-  d.SW = softmax_width(classes);
-  const bool fast = filter == 16 && stride == 5;  // the CFA-GE CNN's geometry: the unrolled kernel
+  const bool fast = cnn_fast(d);
   const void* kern = fast ? (const void*)local_sgd_cnn_kernel<16, 5> : (const void*)local_sgd_cnn_kernel<0, 0>;
   size_t bytes = 0;
-  if (int rc = sgd_lds(fn, kern, cnn_sgd_lds(d, batch_rows), bytes)) return rc;
+  if (int rc = sgd_lds(fn, kern, d.P, cnn_sgd_lds(d, batch_rows), bytes)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (fast)
     local_sgd_cnn_kernel<16, 5><<<(unsigned)D, kGradBlock, bytes, st>>>(a, d);
@@ -525,23 +314,15 @@ extern "C" int cfa_local_sgd_2nn_f32(const float* x, const float* y, int Ns, int
                                      int steps, float lr, int update, double* cost, double* cost_log,
                                      int log_cap, unsigned long long* epoch, void* stream) {
   const char* fn = "cfa_local_sgd_2nn_f32";
-  if (L < 1 || hidden < 1 || classes < 1)
-    return fail(CFA_E_INVALID, "%s: bad dimensions (L %d H %d C %d)", fn, L, hidden, classes);
   NnGeom d;
-  d.L = L, d.H = hidden, d.C = classes;
-  d.G = (L + kSpan - 1) / kSpan;
-  const long long P = (long long)L * hidden + hidden + (long long)hidden * classes + classes;
+  if (int rc = nn_geom(fn, L, hidden, classes, d)) return rc;
   SgdArgs a;
   if (int rc = sgd_args(fn, x, y, Ns, models, pitch, D, batch_stride, batch_rows, steps, lr, update, cost, cost_log,
-                        log_cap, epoch, P, a))
+                        log_cap, epoch, d.P, a))
     return rc;
   if (D == 0) return CFA_OK;
-  if (classes > 64) return fail(CFA_E_UNSUPPORTED, "%s: more than 64 classes", fn);
-  if (P > (1 << 20)) return fail(CFA_E_UNSUPPORTED, "%s: a model of %lld parameters does not fit the LDS", fn, P);
-  d.P = (int)P;
-  d.SW = softmax_width(classes);
   size_t bytes = 0;
-  if (int rc = sgd_lds(fn, (const void*)local_sgd_2nn_kernel, nn_sgd_lds(d, batch_rows), bytes)) return rc;
+  if (int rc = sgd_lds(fn, (const void*)local_sgd_2nn_kernel, d.P, nn_sgd_lds(d, batch_rows), bytes)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   local_sgd_2nn_kernel<<<(unsigned)D, kGradBlock, bytes, st>>>(a, d);
   return sgd_finish("local_sgd_2nn_kernel", a, epoch, st);
