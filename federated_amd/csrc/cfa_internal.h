@@ -130,6 +130,8 @@ inline int device_lds_max() { return device_attr(1, hipDeviceAttributeMaxSharedM
 int grad_prepare_device();
 // cfa_local_sgd.hip: the same for the local-SGD kernels.
 int local_sgd_prepare_device();
+// cfa_lenet.hip: the same for the LeNet-family evaluation kernels.
+int lenet_prepare_device();
 // cfa_population.hip: one-thread launch that leaves a device counter (a schedule's round, a cost
 // log's epoch) one higher, in stream order.
 int advance_counter(unsigned long long* counter, hipStream_t st);

@@ -1,0 +1,194 @@
+// cfa_lenet.hip — the validation pass of a TF2 LeNet-1 population: every device's model run forward
+// over the test set in batches, the mean batch loss and the training_end flag it raises
+// (federated_learning_keras_consensus_FL_threads_MNIST_crossentropy_gradients_exchange.py:430-455,
+// the model of :158-194), on the forward phases of cfa_lenet_graph.h. Forward only: no gradient.
+//
+// Launch 1, grid (batch groups, D): a workgroup stages its device's model into LDS once and owns
+// whole batches b = blockIdx.x, blockIdx.x + gridDim.x, ... A batch goes through the phases in
+// chunks of kLenetChunk samples; each sample's loss lands in LDS and thread 0 sums the batch in
+// sample order, so the fp32 batch loss workspace[d][b] has one owner and does not depend on the
+// grid. A device flagged in `skip` does no work. Launch 2, one workgroup: a thread per device sums
+// its batch losses in fp64 in batch order, writes cost, log entry and flag, and after every thread
+// has read the log's epoch counter one thread leaves it one higher. No atomics; a call is
+// deterministic.
+#include "cfa_lenet_graph.h"
+
+namespace {
+
+constexpr int kLenetBlock = 256;  // 4 waves; several workgroups share a CU and overlap their barriers
+constexpr int kLenetChunk = 4;    // samples per pass through the phases
+
+struct LenetArgs {
+  const float* x;         // [Nt][side][side], or [D][Nt][side][side] with x_stride
+  const int32_t* labels;  // [Nt], or [D][Nt] with label_stride
+  long long x_stride, label_stride;
+  const float* models;    // [D][pitch]
+  long long pitch;
+  int batch, batches;
+  const int32_t* skip;    // [D] or null
+  float* ws;              // [D][batches] batch losses
+};
+
+// LDS floats of the evaluation kernel: the model, a chunk's activations, a batch's losses.
+inline long long lenet_eval_lds(const LenetGeom& g, int batch) {
+  return g.P + (long long)kLenetChunk * lenet_sample_floats(g) + batch;
+}
+
+template <int K>
+__global__ __launch_bounds__(kLenetBlock) void lenet_eval_kernel(LenetArgs a, LenetGeom g) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int dv = blockIdx.y;
+  if (a.skip && a.skip[dv]) return;  // the whole workgroup: the device has left its loop
+  const int tid = threadIdx.x, T = blockDim.x;
+  const int nx = g.side * g.side, n1 = g.p1 * g.p1 * g.c1;
+  float* m = lds;                        // [P]
+  float* xs = m + (int)g.P;              // [chunk][side][side]
+  float* a1 = xs + kLenetChunk * nx;     // [chunk][p1][p1][c1]
+  float* a2 = a1 + kLenetChunk * n1;     // [chunk][flat]
+  float* zl = a2 + kLenetChunk * g.flat; // [chunk][C]
+  float* loss = zl + kLenetChunk * g.C;  // [batch]
+  const float* xd = a.x + (long long)dv * a.x_stride;
+  const int32_t* ld = a.labels + (long long)dv * a.label_stride;
+  stage(m, a.models + (long long)dv * a.pitch, (int)g.P, tid, T);
+  for (int b = blockIdx.x; b < a.batches; b += gridDim.x) {
+    const long long first = (long long)b * a.batch;
+    for (int s0 = 0; s0 < a.batch; s0 += kLenetChunk) {
+      const int ns = min(kLenetChunk, a.batch - s0);
+      // the previous chunk's last read of xs was its first phase, three barriers ago
+      stage(xs, xd + (first + s0) * nx, ns * nx, tid, T);
+      __syncthreads();  // also the model's, the first time
+      lenet_conv_pool<K>(a1, xs, m + g.oK1, m + g.ob1, ns, g.side, 1, g.c1, g.k, g.p1, tid, T);
+      __syncthreads();
+      lenet_conv_pool<K>(a2, a1, m + g.oK2, m + g.ob2, ns, g.p1, g.c1, g.c2, g.k, g.p2, tid, T);
+      __syncthreads();
+      lenet_logits(zl, a2, m + g.oWd, m + g.obd, ns, g.flat, g.C, tid, T);
+      __syncthreads();
+      lenet_xent(loss + s0, zl, ld + first + s0, ns, g.C, tid, T);
+    }
+    __syncthreads();
+    if (tid == 0) {  // reduce_mean over the batch, fp32, in sample order
+      float c = 0.f;
+      for (int s = 0; s < a.batch; ++s) c += loss[s];
+      a.ws[(long long)dv * a.batches + b] = c / (float)a.batch;
+    }
+    // the next batch writes loss only after four more barriers
+  }
+}
+
+struct LenetFinish {
+  const float* ws;
+  int D, batches;
+  const int32_t* skip;
+  double target;
+  int32_t* ended;  // or null
+  double* cost;
+  double* cost_log;  // or null
+  int log_cap;
+  unsigned long long* epoch;  // or null, with cost_log
+};
+
+// One workgroup. Thread d % T owns device d: its cost, its flag (read before it is written, so
+// skip and ended may be one array) and its log entry.
+__global__ __launch_bounds__(kLenetBlock) void lenet_finish_kernel(LenetFinish f) {
+  unsigned long long row = 0;
+  if (f.cost_log) {
+    const unsigned long long e = *f.epoch, last = (unsigned long long)(f.log_cap - 1);
+    row = e < last ? e : last;
+  }
+  for (int d = threadIdx.x; d < f.D; d += blockDim.x) {
+    double c;
+    if (f.skip && f.skip[d]) {
+      c = f.cost[d];
+    } else {
+      double acc = 0.0;
+      for (int b = 0; b < f.batches; ++b) acc += (double)f.ws[(long long)d * f.batches + b];
+      c = acc / (double)f.batches;
+      f.cost[d] = c;
+      if (f.ended) f.ended[d] = f.ended[d] | (c < f.target ? 1 : 0);
+    }
+    if (f.cost_log) f.cost_log[row * (unsigned long long)f.D + d] = c;
+  }
+  if (f.cost_log) {
+    __syncthreads();  // every thread has read the counter
+    if (threadIdx.x == 0) *f.epoch = *f.epoch + 1;
+  }
+}
+
+// The kernel side the evaluation kernel is instantiated for: LeNet-1's 5, every other one 0.
+inline bool lenet_fast(const LenetGeom& g) { return g.k == 5; }
+
+}  // namespace
+
+// Current device: raise the evaluation kernels' dynamic-LDS limit now (cfa_device_prepare), so
+// later launches (e.g. under hipGraph capture) need no attribute call.
+int lenet_prepare_device() {
+  const int lim = device_lds_max();
+  if (lim <= 65536) return CFA_OK;
+  const void* kernels[] = {(const void*)lenet_eval_kernel<5>, (const void*)lenet_eval_kernel<0>};
+  for (const void* k : kernels) (void)raise_lds_limit(k, lim);  // refused: launches stay within 64 KiB
+  return CFA_OK;
+}
+
+extern "C" size_t cfa_lenet_params(int side, int kernel, int c1, int c2, int classes) {
+  LenetGeom g;
+  return lenet_geom(side, kernel, c1, c2, classes, g) ? (size_t)g.P : 0;
+}
+
+extern "C" size_t cfa_lenet_eval_workspace_bytes(int D, int batches) {
+  return D < 1 || batches < 1 ? 0 : (size_t)D * (size_t)batches * sizeof(float);
+}
+
+extern "C" int cfa_lenet_eval_f32(const float* x, size_t x_dev_stride, const int32_t* labels, size_t label_dev_stride,
+                                  int Nt, int side, int kernel, int c1, int c2, int classes, const float* models,
+                                  size_t pitch, int D, int batch, int batches, const int32_t* skip, double target,
+                                  int32_t* ended, double* cost, double* cost_log, int log_cap,
+                                  unsigned long long* epoch, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "cfa_lenet_eval_f32";
+  if (!x || !labels || !models || !cost || !workspace) return fail(CFA_E_INVALID, "%s: null buffer", fn);
+  if (D < 1 || batch < 1 || batches < 1 || Nt < 1)
+    return fail(CFA_E_INVALID, "%s: D %d, batch %d, batches %d and Nt %d must be >= 1", fn, D, batch, batches, Nt);
+  LenetGeom g;
+  if (!lenet_geom(side, kernel, c1, c2, classes, g))
+    return fail(CFA_E_INVALID, "%s: bad geometry (side %d kernel %d c1 %d c2 %d classes %d): every dimension >= 1 "
+                "and a second pooled map of at least 1 x 1", fn, side, kernel, c1, c2, classes);
+  if ((long long)batch * batches > Nt)
+    return fail(CFA_E_INVALID, "%s: %d batches of %d samples do not fit the %d of the test set", fn, batches, batch,
+                Nt);
+  if ((long long)pitch < g.P)
+    return fail(CFA_E_INVALID, "%s: pitch %zu below the model's %lld parameters", fn, pitch, g.P);
+  const long long set = (long long)Nt * side * side;
+  if ((x_dev_stride != 0 && (long long)x_dev_stride < set) || (label_dev_stride != 0 && (long long)label_dev_stride < Nt))
+    return fail(CFA_E_INVALID, "%s: device strides %zu / %zu below one device's set (%lld / %d)", fn, x_dev_stride,
+                label_dev_stride, set, Nt);
+  if ((cost_log == nullptr) != (epoch == nullptr))
+    return fail(CFA_E_INVALID, "%s: cost_log and epoch are given together or not at all", fn);
+  if (cost_log && log_cap < 1) return fail(CFA_E_INVALID, "%s: log_cap %d must be >= 1", fn, log_cap);
+  if (workspace_bytes < cfa_lenet_eval_workspace_bytes(D, batches))
+    return fail(CFA_E_INVALID, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes,
+                cfa_lenet_eval_workspace_bytes(D, batches));
+  if (ended && !std::isfinite(target)) return fail(CFA_E_INVALID, "%s: target must be finite", fn);
+  if (classes > 64) return fail(CFA_E_UNSUPPORTED, "%s: more than 64 classes", fn);
+  if (D > 65535) return fail(CFA_E_UNSUPPORTED, "%s: more than 65535 devices", fn);
+  // the kernel indexes the model and the LDS with ints
+  const bool fast = lenet_fast(g);
+  const void* kern = fast ? (const void*)lenet_eval_kernel<5> : (const void*)lenet_eval_kernel<0>;
+  const long long need = g.P > (1 << 20) ? -1 : 4 * lenet_eval_lds(g, batch), limit = device_lds_max();
+  if (need < 0 || need > limit || (need > 65536 && !raise_lds_limit(kern, (int)limit)))
+    return fail(CFA_E_UNSUPPORTED, "%s: a model of %lld parameters, %d samples' activations and a batch of %d losses "
+                "do not fit one workgroup's LDS", fn, g.P, kLenetChunk, batch);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const LenetArgs a{x, labels, (long long)x_dev_stride, (long long)label_dev_stride, models, (long long)pitch,
+                    batch, batches, skip, static_cast<float*>(workspace)};
+  // about four workgroups per CU over all devices, and every batch group the same number of
+  // batches (but the last)
+  const int per = (batches + (int)shared_grid_x(batches, 4, D) - 1) / (int)shared_grid_x(batches, 4, D);
+  const dim3 grid((unsigned)((batches + per - 1) / per), (unsigned)D);
+  if (fast)
+    lenet_eval_kernel<5><<<grid, kLenetBlock, (size_t)need, st>>>(a, g);
+  else
+    lenet_eval_kernel<0><<<grid, kLenetBlock, (size_t)need, st>>>(a, g);
+  if (int rc = check_launch("lenet_eval_kernel")) return rc;
+  const LenetFinish f{a.ws, D, batches, skip, target, ended, cost, cost_log, log_cap, epoch};
+  lenet_finish_kernel<<<1, kLenetBlock, 0, st>>>(f);
+  return check_launch("lenet_finish_kernel");
+}

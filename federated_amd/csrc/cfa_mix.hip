@@ -38,6 +38,7 @@ extern "C" int cfa_device_prepare(int device) {
   (void)device_cus();  // fills the shared CU-count cache
   int rc = grad_prepare_device();
   if (rc == CFA_OK) rc = local_sgd_prepare_device();
+  if (rc == CFA_OK) rc = lenet_prepare_device();
   if (device != prev) CFA_HIP_CHECK(hipSetDevice(prev));
   return rc;
 }

@@ -553,6 +553,79 @@ class Engine:
             raise ValueError("ml_model must be 1 (CNN) or 2 (2NN)")
         return models
 
+    # -- validation pass of a TF2 LeNet-1 population ------------------------------------------
+    def lenet_params(self, geom: Sequence[int]) -> int:
+        """Parameters of a LeNet-family model (cfa_lenet_params); 0 for a geometry without one."""
+        return int(_lib.load().cfa_lenet_params(*(int(v) for v in geom)))
+
+    def lenet_workspace(self, D: int, batches: int) -> torch.Tensor:
+        """Workspace of the batch losses (cfa_lenet_eval_workspace_bytes)."""
+        n = int(_lib.load().cfa_lenet_eval_workspace_bytes(int(D), int(batches)))
+        return torch.empty(max(n // 4, 1), dtype=torch.float32, device=self.device)
+
+    def lenet_eval(self, geom: Sequence[int], x: torch.Tensor, labels: torch.Tensor, models: torch.Tensor,
+                   batch: int, batches: int, cost: torch.Tensor, workspace: torch.Tensor,
+                   skip: Optional[torch.Tensor] = None, target: float = 0.0, ended: Optional[torch.Tensor] = None,
+                   cost_log: Optional[torch.Tensor] = None, epoch: Optional[torch.Tensor] = None,
+                   stream=None) -> torch.Tensor:
+        """cfa_lenet_eval_f32: the validation cost of every device of ``models`` [D, P] (fp32 CUDA,
+        unit element stride, any row pitch, read only; get_weights() order) on the LeNet-family
+        ``geom`` = (side, kernel, c1, c2, classes), over ``batches`` batches of ``batch`` samples
+        of the test set ``x`` [Nt, side, side] fp32 / ``labels`` [Nt] int32 that all devices share,
+        or ``x`` [D, Nt, side, side] / ``labels`` [D, Nt] with one set per device (all contiguous
+        CUDA). ``cost`` [D] fp64 CUDA receives each device's mean batch loss. ``skip`` [D] int32
+        CUDA flags or None: a flagged device's cost and flag are not touched. ``ended`` [D] int32
+        CUDA or None: ``ended[d] |= cost[d] < target``; it may be ``skip`` itself. ``cost_log``
+        [cap, D] fp64 CUDA and ``epoch`` (one-element int64 CUDA counter), given together: as
+        ``local_sgd``. ``workspace``: ``lenet_workspace(D, batches)``. The library validates the
+        rest (CFAError)."""
+        geom = tuple(int(v) for v in geom)
+        if len(geom) != 5:
+            raise ValueError("geom must be (side, kernel, c1, c2, classes)")
+        side = geom[0]
+        D, P = _check_nd(models, "models", pitched=True)
+        if x.dim() == 3:
+            Nt = _check_nd(x, "x", 3)[0]
+            x_stride = label_stride = 0
+            shapes = ((Nt, side, side), (Nt,))
+        else:
+            Nt = _check_nd(x, "x", 4, what="[Nt, side, side] or [D, Nt, side, side]")[1]
+            x_stride, label_stride = Nt * side * side, Nt
+            shapes = ((D, Nt, side, side), (D, Nt))
+        _check_tables(("labels", labels, torch.int32))
+        if (tuple(x.shape), tuple(labels.shape)) != shapes:
+            raise ValueError(f"x and labels must be {shapes[0]} and {shapes[1]} for these models and this geometry")
+        if P != self.lenet_params(geom):
+            raise ValueError("models' row size does not match the geometry")
+        batch, batches = int(batch), int(batches)
+        if batch < 1 or batches < 1 or batch * batches > Nt:
+            raise ValueError(f"{batches} batches of {batch} samples do not fit the {Nt} of the test set")
+        _check_bucket(cost, "cost", D, torch.float64)
+        for name, t in (("skip", skip), ("ended", ended)):
+            if t is not None:
+                _check_tables((name, t, torch.int32))
+                if t.numel() != D:
+                    raise ValueError(f"{name} must hold one int32 flag per device")
+        if (cost_log is None) != (epoch is None):
+            raise ValueError("cost_log and epoch are given together or not at all")
+        cap = 0
+        if cost_log is not None:
+            _check_tables(("cost_log", cost_log, torch.float64), ("epoch", epoch, torch.int64))
+            if cost_log.dim() != 2 or cost_log.shape[1] != D or cost_log.shape[0] < 1 or epoch.numel() != 1:
+                raise ValueError("cost_log must be [cap >= 1, D] and epoch a one-element counter")
+            cap = int(cost_log.shape[0])
+        _check_tables(("workspace", workspace, torch.float32))
+        pitch = int(models.stride(0)) if D > 1 else P
+        if pitch < P:
+            raise ValueError("models rows overlap (pitch below P)")
+        _lib.call("cfa_lenet_eval_f32", x.data_ptr(), x_stride, labels.data_ptr(), label_stride, Nt, *geom,
+                  models.data_ptr(), pitch, D, batch, batches, skip.data_ptr() if skip is not None else None,
+                  float(target), ended.data_ptr() if ended is not None else None, cost.data_ptr(),
+                  cost_log.data_ptr() if cost_log is not None else None, cap,
+                  epoch.data_ptr() if epoch is not None else None, workspace.data_ptr(), workspace.numel() * 4,
+                  self.stream_handle(stream))
+        return cost
+
     # -- local optimizer step of a TF2 population ---------------------------------------------
     def optim_tile(self) -> int:
         """Elements of a tile of the optimizer step (cfa_optim_tile)."""
@@ -883,7 +956,7 @@ _engines: dict = {}
 for _name, _fn in list(vars(Engine).items()):
     if (callable(_fn) and not isinstance(_fn, (staticmethod, classmethod)) and not _name.startswith("_")
             and _name not in ("empty", "counter", "stream_handle", "grad_workspace", "grad_splits", "optim_tile",
-                              "optim_workspace")):
+                              "optim_workspace", "lenet_params", "lenet_workspace")):
         setattr(Engine, _name, _same_device(_fn))
 
 

@@ -6,6 +6,9 @@
  * inside its `consensus` package. Each entry point below replaces one of those chains
  * (citations are `path:line` under the reference tree; TF1 = tensorflow1_implementations,
  * TF2 = tensorflow2_implementations/MNIST_dataset unless stated).
+ * The blocks marked (f3/f4) and (TF2 drivers) cover what a driver does on every device between
+ * two mixing steps: the TF1 local SGD epoch, the TF2 optimizer step and the TF2 validation pass
+ * (the forward pass of the LeNet-1 family and the training_end flag; no Keras gradient).
  *
  * Conventions
  *   - Plain pointers and sizes only. Buffers are caller-owned device pointers
@@ -637,6 +640,59 @@ CFA_API int cfa_optim_step_f32(float* models, size_t pitch, const float* grads, 
                                double* pow, int rule, float lr, float momentum, double beta_1, double beta_2,
                                float epsilon, float clipnorm, void* workspace, size_t workspace_bytes, int D,
                                size_t P, void* stream);
+
+/* (TF2 drivers) The validation pass of a LeNet-1 population and the training_end flag it raises:
+ * what every device does once per epoch in
+ * federated_learning_keras_consensus_FL_threads_MNIST_crossentropy_gradients_exchange.py:430-455
+ * with the model of create_q_model, condition 0 (:158-194). Forward only: no gradient, no step.
+ * The model family, Keras semantics, geometry (side, kernel, c1, c2, classes):
+ *   x [side, side, 1] -> Conv2D(c1, kernel x kernel, valid, relu) -> AveragePooling2D(2 x 2)
+ *     -> Conv2D(c2, kernel x kernel, valid, relu) -> AveragePooling2D(2 x 2) -> Flatten (NHWC)
+ *     -> Dense(classes, softmax)
+ * Conv2D is a cross-correlation with the kernel tensor (kh, kw, in, out); pooling drops an odd
+ * last row and column. A model row is get_weights() order, C-order: K1 (k,k,1,c1), b1, K2
+ * (k,k,c1,c2), b2, Wd (flat, classes), bd, with s1 = side-k+1, p1 = s1/2, s2 = p1-k+1, p2 = s2/2,
+ * flat = p2*p2*c2 and P = k*k*c1 + c1 + k*k*c1*c2 + c2 + flat*classes + classes = cfa_lenet_params
+ * (0 for a geometry without a model). LeNet-1 is (28, 5, 4, 8, 10), P = 2202.
+ *   x       [Nt, side, side] fp32 and labels [Nt] int32 (values in [0, classes); the caller
+ *           checks them: a label outside gives a NaN cost): the test set all devices share, with
+ *           both device strides 0. A non-zero stride (in elements) gives device d its own set at
+ *           x + d * x_dev_stride / labels + d * label_dev_stride.
+ *   models  [D, pitch] fp32, pitch >= P, read only; rows need no alignment.
+ *   skip    [D] int32 or NULL: a device with a non-zero flag has left its loop (:498); its cost
+ *           and flag are not touched.
+ * For every other device d:
+ *   for b in 0 .. batches-1: loss_b = mean over samples [b*batch, (b+1)*batch) of
+ *       -log softmax(z)[label]                                    (fp32)
+ *   cost[d] = (sum_b (double)loss_b) / batches                    (fp64, in batch order)
+ *   ended != NULL: ended[d] = ended[d] | (cost[d] < target)
+ * skip and ended may be the same array (a population's flags): each flag has one owner, which
+ * reads it before writing it. cost_log [log_cap, D] (fp64) and epoch (one device counter) are
+ * given together or both NULL and work as in the cfa_local_sgd_* block: row min(*epoch, log_cap-1)
+ * receives every device's cost[d] (a skipped device's untouched one) and *epoch is left one higher
+ * in stream order. workspace: at least cfa_lenet_eval_workspace_bytes(D, batches) bytes of DEVICE
+ * memory (the fp32 batch losses).
+ * Every operation is fp32 (no contraction); the log-probability is z - max - log(sum exp(z - max)).
+ * The reference takes log of the softmax output (:442): the two agree to rounding wherever no
+ * class probability underflows; where one does the reference yields inf / nan and this a finite
+ * cost. Its avg_cost += loss / n is fp32 under numpy 2 and fp64 under numpy 1: fp64 here.
+ * Deterministic: every output has one owner and every sum a fixed order, no atomics; a batch's
+ * loss depends neither on how batches are dealt to workgroups nor on d. No host read, allocation
+ * or attribute call: capture-safe. Two launches, none per device, batch or layer.
+ * CFA_E_INVALID: a null x, labels, models, cost or workspace; D, batch, batches, c1, c2, classes
+ * or kernel < 1; a geometry with p2 < 1; batch*batches > Nt; pitch < P; a non-zero device stride
+ * below one device's set; only one of cost_log / epoch; a workspace too small; a non-finite target
+ * with ended. CFA_E_UNSUPPORTED: classes > 64, D > 65535, or a model, four samples' activations
+ * and a batch of losses beyond one workgroup's LDS (raised to the device's 160 KiB by
+ * cfa_device_prepare), e.g. (28, 3, 32, 64, 10) with P = 34826: refused, not approximated. */
+CFA_API size_t cfa_lenet_params(int side, int kernel, int c1, int c2, int classes);  /* 0: invalid geometry */
+CFA_API size_t cfa_lenet_eval_workspace_bytes(int D, int batches);
+CFA_API int cfa_lenet_eval_f32(const float* x, size_t x_dev_stride, const int32_t* labels, size_t label_dev_stride,
+                               int Nt, int side, int kernel, int c1, int c2, int classes,
+                               const float* models, size_t pitch, int D, int batch, int batches,
+                               const int32_t* skip, double target, int32_t* ended,
+                               double* cost, double* cost_log, int log_cap, unsigned long long* epoch,
+                               void* workspace, size_t workspace_bytes, void* stream);
 
 /* (a1-a6 batched) Population round: one launch mixes D devices.
  * For device d, CSR entries e in [csr_ptr[d], csr_ptr[d+1]) list its sources in order; the
