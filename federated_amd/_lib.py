@@ -150,6 +150,10 @@ SIGNATURES = {
                                     _c_int, _c_void_p, _c_size_t, _c_int, _c_int, _c_int, _c_void_p, ctypes.c_double,
                                     _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_size_t,
                                     _c_void_p]),
+    "cfa_lenet_grad_workspace_bytes": (_c_size_t, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int]),
+    "cfa_lenet_grad_f32": (_c_int, [_c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_int, _c_int, _c_int, _c_int, _c_int,
+                                    _c_int, _c_void_p, _c_size_t, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p,
+                                    _c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "cfa_optim_tile": (_c_int, []),
     "cfa_optim_workspace_bytes": (_c_size_t, [_c_int, _c_size_t, _c_int]),
     "cfa_optim_step_f32": (_c_int, [_c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t,

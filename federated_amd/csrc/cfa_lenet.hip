@@ -1,7 +1,7 @@
 // cfa_lenet.hip — the validation pass of a TF2 LeNet-1 population: every device's model run forward
 // over the test set in batches, the mean batch loss and the training_end flag it raises
 // (federated_learning_keras_consensus_FL_threads_MNIST_crossentropy_gradients_exchange.py:430-455,
-// the model of :158-194), on the forward phases of cfa_lenet_graph.h. Forward only: no gradient.
+// the model of :158-194), on the forward phases of cfa_lenet_graph.h. Forward only: the gradient is cfa_lenet_grad.hip.
 //
 // Launch 1, grid (batch groups, D): a workgroup stages its device's model into LDS once and owns
 // whole batches b = blockIdx.x, blockIdx.x + gridDim.x, ... A batch goes through the phases in
@@ -123,10 +123,10 @@ inline bool lenet_fast(const LenetGeom& g) { return g.k == 5; }
 // later launches (e.g. under hipGraph capture) need no attribute call.
 int lenet_prepare_device() {
   const int lim = device_lds_max();
-  if (lim <= 65536) return CFA_OK;
+  if (lim <= 65536) return CFA_OK;  // nor would the gradient kernels' be raised
   const void* kernels[] = {(const void*)lenet_eval_kernel<5>, (const void*)lenet_eval_kernel<0>};
   for (const void* k : kernels) (void)raise_lds_limit(k, lim);  // refused: launches stay within 64 KiB
-  return CFA_OK;
+  return lenet_grad_prepare_device();
 }
 
 extern "C" size_t cfa_lenet_params(int side, int kernel, int c1, int c2, int classes) {

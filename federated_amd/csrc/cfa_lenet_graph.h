@@ -1,7 +1,9 @@
-// cfa_lenet_graph.h — the forward pass of the TF2 drivers' "LeNet-1 family" (create_q_model,
-// condition 0, federated_learning_keras_consensus_FL_threads_MNIST_crossentropy_gradients_exchange.py
-// :158-194), written once as phases for the kernels that evaluate it (cfa_lenet.hip: the validation
-// cost; a gradient kernel would run the same forward phases), and the family's geometry on the host.
+// cfa_lenet_graph.h — the forward and backward pass of the TF2 drivers' "LeNet-1 family"
+// (create_q_model, condition 0,
+// federated_learning_keras_consensus_FL_threads_MNIST_crossentropy_gradients_exchange.py:158-194),
+// written once as phases for the kernels that evaluate it (cfa_lenet.hip: the validation cost;
+// cfa_lenet_grad.hip: a minibatch's gradient on the same forward phases), and the family's geometry
+// on the host.
 //   x [side, side, 1] -> Conv2D(c1, k x k, valid) + b1 -> relu -> AveragePooling2D(2 x 2, stride 2)
 //     -> Conv2D(c2, k x k, valid) + b2 -> relu -> AveragePooling2D(2 x 2) -> Flatten -> Dense(classes)
 //   loss = -log softmax(z)[label], evaluated as -(z_l - max - log(sum exp(z - max)))
@@ -17,6 +19,25 @@
 // workgroup calls (tid of T); the caller puts the barriers between phases. Every sample's
 // arithmetic is its own and every sum has a fixed order, so a sample's loss does not depend on
 // which chunk, workgroup or device evaluates it. fp32 throughout. Not installed, not an ABI.
+//
+// Backward (per sample; the 1 / batch factor belongs to the caller's finishing step):
+//   dz[c] = exp(z_c - max) / sum - (c == l), with the forward's own max and sum
+//   dWd[i][c] = flat[i] dz[c], dbd[c] = dz[c], dflat[i] = sum_c Wd[i][c] dz[c]
+//   pool: each of a window's four positions receives 0.25 d(pooled); a dropped row or column none
+//   relu: the forward's own test z > 0 (z == 0 passes nothing, as TF's ReluGrad)
+//   conv: dK[ky][kx][ci][co] = sum_{y,x} in[y+ky][x+kx][ci] dzc[y][x][co], db[co] = sum_{y,x} dzc[y][x][co],
+//         stage 2 also din[y][x][ci] = sum over the taps that reach (y, x) of K[ky][kx][ci][co] dzc[y-ky][x-kx][co]
+// The gates are STORED, as bits: the forward phase's optional output is one byte per pooled
+// element whose bit 2 dy + dx is the test of window position (dy, dx), so a gate costs a quarter
+// of a byte where a float mask would cost four. A gated gradient is (bit ? 0.25 : 0) * d(pooled)
+// (LenetGated), a product, so that a NaN upstream (a label out of range) reaches every element.
+// Stage 2's is written out once (it is read k * k * c1 times by the input gradient), stage 1's
+// is formed where it is read. LDS of the gradient kernel, in floats, for a chunk of n samples and a
+// group of g: 2 P (model, gradient sums) + n (side^2 + 2 p1^2 c1 + 2 flat + 2 C + 4 p2^2 c2) + g + n
+// + ceil(n (p1^2 c1 + flat) / 4) (lenet_grad_lds in cfa_lenet_grad.hip; LeNet-1 at n = 2, g = 4: 39.9 KiB).
+// A weight gradient is summed in a fixed order: the rows (sample, y) of a chunk are dealt to L
+// lanes (L a power of two from the geometry alone), each lane sums its rows in order, x in order,
+// from 0, the lanes are folded by xor-shuffles, and the chunk's sum is added to the running one.
 #pragma once
 #include "cfa_grad_common.h"
 
@@ -74,10 +95,12 @@ inline long long lenet_sample_floats(const LenetGeom& g) {
 // adds the bias last, and the window is summed (0,0) (0,1) (1,0) (1,1) and scaled by 0.25 (exact).
 // K > 0: the kernel side at compile time (the tap loops unroll, and the window's (K + 1)^2 inputs
 // are loaded once); K = 0: any side. The arithmetic and its order are the same either way.
+// gate (or null): [ns][pout][pout][cout] bytes, bit 2 dy + dx set where z[2py + dy][2px + dx] > 0.
 template <int K>
 __device__ __forceinline__ void lenet_conv_pool(float* __restrict__ out, const float* __restrict__ in,
                                                 const float* __restrict__ W, const float* __restrict__ b, int ns,
-                                                int sin, int cin, int cout, int kside, int pout, int tid, int T) {
+                                                int sin, int cin, int cout, int kside, int pout, int tid, int T,
+                                                uint8_t* __restrict__ gate = nullptr) {
   const int k = K > 0 ? K : kside;
   const int per = pout * pout * cout, row = sin * cin;
   for (int idx = tid; idx < ns * per; idx += T) {
@@ -109,6 +132,7 @@ __device__ __forceinline__ void lenet_conv_pool(float* __restrict__ out, const f
     const float h00 = z00 > 0.f ? z00 : 0.f, h01 = z01 > 0.f ? z01 : 0.f;
     const float h10 = z10 > 0.f ? z10 : 0.f, h11 = z11 > 0.f ? z11 : 0.f;
     out[idx] = (((h00 + h01) + h10) + h11) * 0.25f;
+    if (gate) gate[idx] = (uint8_t)((z00 > 0.f ? 1 : 0) | (z01 > 0.f ? 2 : 0) | (z10 > 0.f ? 4 : 0) | (z11 > 0.f ? 8 : 0));
   }
 }
 
@@ -129,9 +153,10 @@ __device__ __forceinline__ void lenet_logits(float* zl, const float* flat, const
 }
 
 // loss[s] = -(z_l - max - log(sum_c exp(z_c - max))) for sample s's label l, one thread per
-// sample, classes in order. A label outside [0, C) reads nothing and gives NaN.
+// sample, classes in order. A label outside [0, C) reads nothing and gives NaN. dz (or null):
+// [ns][C], the loss's gradient at the logits, exp(z_c - max) / sum - (c == l); all NaN for such a label.
 __device__ __forceinline__ void lenet_xent(float* loss, const float* zl, const int32_t* labels, int ns, int C,
-                                           int tid, int T) {
+                                           int tid, int T, float* dz = nullptr) {
   for (int s = tid; s < ns; s += T) {
     const float* z = zl + s * C;
     float mx = z[0];
@@ -140,6 +165,168 @@ __device__ __forceinline__ void lenet_xent(float* loss, const float* zl, const i
     for (int c = 0; c < C; ++c) sum += expf(z[c] - mx);
     const int l = labels[s];
     loss[s] = (unsigned)l < (unsigned)C ? -((z[l] - mx) - logf(sum)) : NAN;
+    if (dz) {
+      const bool ok = (unsigned)l < (unsigned)C;
+      for (int c = 0; c < C; ++c) dz[s * C + c] = ok ? expf(z[c] - mx) / sum - (c == l ? 1.f : 0.f) : NAN;
+    }
+  }
+}
+
+// ---- backward phases --------------------------------------------------------------------------
+
+// The dense layer's backward for ns samples: gWd[i][c] += sum_s flat[s][i] dz[s][c] and
+// gbd[c] += sum_s dz[s][c] (one thread per element, samples in order, onto the running sum), and
+// dflat[s][i] = sum_c Wd[i][c] dz[s][c], classes in order from 0.
+__device__ __forceinline__ void lenet_dense_backward(float* gWd, float* gbd, float* dflat, const float* flat,
+                                                     const float* dz, const float* Wd, int ns, int F, int C, int tid,
+                                                     int T) {
+  for (int e = tid; e < F * C; e += T) {
+    const int i = e / C, c = e % C;
+    float a = gWd[e];
+    for (int s = 0; s < ns; ++s) a = fmaf(flat[s * F + i], dz[s * C + c], a);
+    gWd[e] = a;
+  }
+  for (int c = tid; c < C; c += T) {
+    float a = gbd[c];
+    for (int s = 0; s < ns; ++s) a += dz[s * C + c];
+    gbd[c] = a;
+  }
+  for (int idx = tid; idx < ns * F; idx += T) {
+    const int s = idx / F, i = idx % F;
+    float a = 0.f;
+    for (int c = 0; c < C; ++c) a = fmaf(Wd[i * C + c], dz[s * C + c], a);
+    dflat[idx] = a;
+  }
+}
+
+// dzc[s][y][x][co] of a stage, y and x below 2 pout (what the pool kept), from the stage's gate
+// bytes and the gradient dp [ns][pout][pout][cout] of its pooled map.
+struct LenetGated {
+  const uint8_t* gate;
+  const float* dp;
+  int pout, cout;
+  __device__ __forceinline__ float operator()(int s, int y, int x, int co) const {
+    const int i = ((s * pout + (y >> 1)) * pout + (x >> 1)) * cout + co;
+    return ((gate[i] >> (2 * (y & 1) + (x & 1))) & 1 ? 0.25f : 0.f) * dp[i];
+  }
+};
+
+// The same values written out: v [ns][side][side][cout], side = 2 pout.
+struct LenetStored {
+  const float* v;
+  int side, cout;
+  __device__ __forceinline__ float operator()(int s, int y, int x, int co) const {
+    return v[((s * side + y) * side + x) * cout + co];
+  }
+};
+
+__device__ __forceinline__ void lenet_store_gated(float* v, const LenetGated& g, int ns, int tid, int T) {
+  const int side = 2 * g.pout;
+  for (int idx = tid; idx < ns * side * side * g.cout; idx += T) {
+    const int co = idx % g.cout, x = (idx / g.cout) % side, y = (idx / (g.cout * side)) % side;
+    v[idx] = g(idx / (g.cout * side * side), y, x, co);
+  }
+}
+
+// Lanes that share one sum of `items` sums among T threads: the largest power of two L <= 64
+// with items * L <= T (1 when there are more sums than threads). T is a multiple of 64, so the L
+// lanes of a sum are neighbours in one wave.
+__device__ __forceinline__ int lenet_lanes(int items, int T) {
+  int L = 1;
+  while (L < 64 && 2 * L * items <= T) L *= 2;
+  return L;
+}
+
+__device__ __forceinline__ float lenet_fold(float v, int L) {
+  for (int m = 1; m < L; m <<= 1) v += __shfl_xor(v, m, L);
+  return v;
+}
+
+// gK[ky][kx][ci][co] += sum_{s,y,x} in[s][y+ky][x+kx][ci] dz(s, y, x, co) over the chunk's ns
+// samples, in [ns][sin][sin][cin]. An item is (ky, ci, co) with all its kx; its rows (s, y) are
+// dealt to L lanes, row r to lane r % L. K > 0: the k inputs under a row's taps slide through
+// registers (one input and one dz read per x for k multiply-adds); K = 0: any side, one sum at
+// a time. Every sum runs over its lane's rows in order and x in order from 0, either way.
+template <int K, class Dz>
+__device__ __forceinline__ void lenet_conv_wgrad(float* gK, const float* in, const Dz& dz, int ns, int sin, int cin,
+                                                 int cout, int kside, int pout, int tid, int T) {
+  const int k = K > 0 ? K : kside;
+  const int items = k * cin * cout, L = lenet_lanes(items, T);
+  const int side = 2 * pout, rows = ns * side;
+  for (int idx = tid; idx < items * L; idx += T) {
+    const int it = idx / L, lane = idx % L;
+    const int co = it % cout, ci = (it / cout) % cin, ky = it / (cout * cin);
+    float* out = gK + (ky * k * cin + ci) * cout + co;  // + kx * cin * cout
+    if constexpr (K > 0) {
+      float acc[K];
+#pragma unroll
+      for (int j = 0; j < K; ++j) acc[j] = 0.f;
+      for (int r = lane; r < rows; r += L) {
+        const int s = r / side, y = r % side;
+        const float* p = in + ((s * sin + y + ky) * sin) * cin + ci;
+        float w[K];  // w[j] = in[.][x + j][ci] once x's input has been shifted in
+#pragma unroll
+        for (int j = 1; j < K; ++j) w[j] = p[(j - 1) * cin];
+        for (int x = 0; x < side; ++x) {
+#pragma unroll
+          for (int j = 0; j + 1 < K; ++j) w[j] = w[j + 1];
+          w[K - 1] = p[(x + K - 1) * cin];
+          const float d = dz(s, y, x, co);
+#pragma unroll
+          for (int j = 0; j < K; ++j) acc[j] = fmaf(w[j], d, acc[j]);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        const float v = lenet_fold(acc[j], L);
+        if (lane == 0) out[j * cin * cout] += v;
+      }
+    } else {
+      for (int kx = 0; kx < k; ++kx) {
+        float acc = 0.f;
+        for (int r = lane; r < rows; r += L) {
+          const int s = r / side, y = r % side;
+          const float* p = in + ((s * sin + y + ky) * sin + kx) * cin + ci;
+          for (int x = 0; x < side; ++x) acc = fmaf(p[x * cin], dz(s, y, x, co), acc);
+        }
+        const float v = lenet_fold(acc, L);
+        if (lane == 0) out[kx * cin * cout] += v;
+      }
+    }
+  }
+}
+
+// gb[co] += sum_{s,y,x} dz(s, y, x, co): the chunk's ns * (2 pout)^2 terms of a channel dealt to
+// L lanes, term t to lane t % L, each lane in order from 0.
+template <class Dz>
+__device__ __forceinline__ void lenet_conv_bgrad(float* gb, const Dz& dz, int ns, int cout, int pout, int tid, int T) {
+  const int L = lenet_lanes(cout, T), side = 2 * pout, terms = ns * side * side;
+  for (int idx = tid; idx < cout * L; idx += T) {
+    const int co = idx / L, lane = idx % L;
+    float acc = 0.f;
+    for (int t = lane; t < terms; t += L) acc += dz(t / (side * side), (t / side) % side, t % side, co);
+    const float v = lenet_fold(acc, L);
+    if (lane == 0) gb[co] += v;
+  }
+}
+
+// din[s][y][x][ci] = sum over the taps (ky, kx) with y - ky and x - kx in [0, 2 pout), in order,
+// and co in order, of W[ky][kx][ci][co] dzc[s][y-ky][x-kx][co]; din [ns][sin][sin][cin], dzc
+// [ns][2 pout][2 pout][cout]. An input no kept output reads receives 0.
+__device__ __forceinline__ void lenet_conv_igrad(float* din, const float* dzc, const float* W, int ns, int sin,
+                                                 int cin, int cout, int k, int pout, int tid, int T) {
+  const int side = 2 * pout;
+  for (int idx = tid; idx < ns * sin * sin * cin; idx += T) {
+    const int ci = idx % cin, x = (idx / cin) % sin, y = (idx / (cin * sin)) % sin, s = idx / (cin * sin * sin);
+    const int ky0 = max(0, y - side + 1), ky1 = min(k - 1, y), kx0 = max(0, x - side + 1), kx1 = min(k - 1, x);
+    float acc = 0.f;
+    for (int ky = ky0; ky <= ky1; ++ky)
+      for (int kx = kx0; kx <= kx1; ++kx) {
+        const float* w = W + ((ky * k + kx) * cin + ci) * cout;
+        const float* d = dzc + ((s * side + y - ky) * side + x - kx) * cout;
+        for (int co = 0; co < cout; ++co) acc = fmaf(w[co], d[co], acc);
+      }
+    din[idx] = acc;
   }
 }
 

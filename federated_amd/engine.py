@@ -626,6 +626,69 @@ class Engine:
                   self.stream_handle(stream))
         return cost
 
+    # -- minibatch gradient of a TF2 LeNet-1 population ---------------------------------------
+    def lenet_grad_workspace(self, D: int, batch: int, geom: Sequence[int]) -> torch.Tensor:
+        """Workspace of the sample groups' partial gradients (cfa_lenet_grad_workspace_bytes)."""
+        n = int(_lib.load().cfa_lenet_grad_workspace_bytes(int(D), int(batch), *(int(v) for v in geom)))
+        return torch.empty(max(n // 4, 1), dtype=torch.float32, device=self.device)
+
+    def lenet_grad(self, geom: Sequence[int], x: torch.Tensor, labels: torch.Tensor, models: torch.Tensor,
+                   batch: int, grads: torch.Tensor, workspace: torch.Tensor, loss: Optional[torch.Tensor] = None,
+                   src: Optional[torch.Tensor] = None, first: Optional[torch.Tensor] = None,
+                   skip: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+        """cfa_lenet_grad_f32: the mean loss and its gradient over one batch of ``batch`` samples
+        for every device of ``models`` [D, P] (fp32 CUDA, unit element stride, any row pitch, read
+        only) on the LeNet-family ``geom``, with the training set ``x`` [Nt, side, side] fp32 /
+        ``labels`` [Nt] int32 all devices share, or [D, Nt, side, side] / [D, Nt] with one set per
+        device (contiguous CUDA). ``grads`` [D, P] fp32 CUDA (unit element stride, any row pitch)
+        receives the gradients and ``loss`` ([D] fp32 CUDA, or None) the batch losses. ``src``
+        ([D] int32 CUDA, or None): device d evaluates row ``src[d]`` of ``models`` on its own
+        data; values outside [0, D) are the caller's error. ``first`` ([D] int64 CUDA, or None
+        for 0): the first sample of every device's batch; a batch past the set's end wraps.
+        ``skip`` ([D] int32 CUDA, or None): a flagged device's row and loss are not touched.
+        ``workspace``: ``lenet_grad_workspace(D, batch, geom)``. The library validates the rest
+        (CFAError)."""
+        geom = tuple(int(v) for v in geom)
+        if len(geom) != 5:
+            raise ValueError("geom must be (side, kernel, c1, c2, classes)")
+        side = geom[0]
+        D, P = _check_nd(models, "models", pitched=True)
+        if x.dim() == 3:
+            Nt = _check_nd(x, "x", 3)[0]
+            x_stride = label_stride = 0
+            shapes = ((Nt, side, side), (Nt,))
+        else:
+            Nt = _check_nd(x, "x", 4, what="[Nt, side, side] or [D, Nt, side, side]")[1]
+            x_stride, label_stride = Nt * side * side, Nt
+            shapes = ((D, Nt, side, side), (D, Nt))
+        _check_tables(("labels", labels, torch.int32))
+        if (tuple(x.shape), tuple(labels.shape)) != shapes:
+            raise ValueError(f"x and labels must be {shapes[0]} and {shapes[1]} for these models and this geometry")
+        if P != self.lenet_params(geom):
+            raise ValueError("models' row size does not match the geometry")
+        batch = int(batch)
+        if batch < 1 or batch > Nt:
+            raise ValueError(f"a batch of {batch} samples does not fit the {Nt} of the training set")
+        if _check_nd(grads, "grads", pitched=True) != (D, P):
+            raise ValueError(f"grads must be [{D}, {P}]")
+        if loss is not None:
+            _check_bucket(loss, "loss", D, torch.float32)
+        for name, t, dt in (("src", src, torch.int32), ("first", first, torch.int64), ("skip", skip, torch.int32)):
+            if t is not None:
+                _check_tables((name, t, dt))
+                if t.numel() != D:
+                    raise ValueError(f"{name} must hold one {dt} entry per device")
+        _check_tables(("workspace", workspace, torch.float32))
+        pitch = int(models.stride(0)) if D > 1 else P
+        gpitch = int(grads.stride(0)) if D > 1 else P
+        if pitch < P or gpitch < P:
+            raise ValueError("models or grads rows overlap (pitch below P)")
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        _lib.call("cfa_lenet_grad_f32", x.data_ptr(), x_stride, labels.data_ptr(), label_stride, Nt, *geom,
+                  models.data_ptr(), pitch, D, ptr(src), ptr(first), batch, ptr(skip), grads.data_ptr(), gpitch,
+                  ptr(loss), workspace.data_ptr(), workspace.numel() * 4, self.stream_handle(stream))
+        return grads
+
     # -- local optimizer step of a TF2 population ---------------------------------------------
     def optim_tile(self) -> int:
         """Elements of a tile of the optimizer step (cfa_optim_tile)."""
@@ -956,7 +1019,7 @@ _engines: dict = {}
 for _name, _fn in list(vars(Engine).items()):
     if (callable(_fn) and not isinstance(_fn, (staticmethod, classmethod)) and not _name.startswith("_")
             and _name not in ("empty", "counter", "stream_handle", "grad_workspace", "grad_splits", "optim_tile",
-                              "optim_workspace", "lenet_params", "lenet_workspace")):
+                              "optim_workspace", "lenet_params", "lenet_workspace", "lenet_grad_workspace")):
         setattr(Engine, _name, _same_device(_fn))
 
 

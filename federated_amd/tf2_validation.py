@@ -16,11 +16,13 @@ The model family is the "LeNet-1 family" ``geom = (side, kernel, c1, c2, classes
                     -> Flatten -> Dense(classes, softmax)
 
 with a model row in ``get_weights()`` order (``lenet_layer_shapes``), the row layout
-``PopulationOptimizer`` and the populations already use. Forward only: the gradients stay the
-caller's. The populations are not edited; the chain of one epoch is::
+``PopulationOptimizer`` and the populations already use. The populations are not edited; the
+chain of one epoch is::
 
     val.validate(pop.models, skip=pop.ended, ended=pop.ended)
+    grads = train.gradients(pop.models, skip=pop.ended)      # tf2_training.LenetTraining
     opt.step(pop.models, grads, pop.ended)
+    train.advance(pop.ended)
     pop.rounds(1)
 
 and all of it may be captured into a graph: ``validate`` reads nothing back.

@@ -7,8 +7,8 @@
  * (citations are `path:line` under the reference tree; TF1 = tensorflow1_implementations,
  * TF2 = tensorflow2_implementations/MNIST_dataset unless stated).
  * The blocks marked (f3/f4) and (TF2 drivers) cover what a driver does on every device between
- * two mixing steps: the TF1 local SGD epoch, the TF2 optimizer step and the TF2 validation pass
- * (the forward pass of the LeNet-1 family and the training_end flag; no Keras gradient).
+ * two mixing steps: the TF1 local SGD epoch, the TF2 optimizer step, the TF2 validation pass (the
+ * forward pass of the LeNet-1 family and the training_end flag) and that family's minibatch gradient.
  *
  * Conventions
  *   - Plain pointers and sizes only. Buffers are caller-owned device pointers
@@ -644,7 +644,7 @@ CFA_API int cfa_optim_step_f32(float* models, size_t pitch, const float* grads, 
 /* (TF2 drivers) The validation pass of a LeNet-1 population and the training_end flag it raises:
  * what every device does once per epoch in
  * federated_learning_keras_consensus_FL_threads_MNIST_crossentropy_gradients_exchange.py:430-455
- * with the model of create_q_model, condition 0 (:158-194). Forward only: no gradient, no step.
+ * with the model of create_q_model, condition 0 (:158-194). Forward only: the gradient is cfa_lenet_grad_f32.
  * The model family, Keras semantics, geometry (side, kernel, c1, c2, classes):
  *   x [side, side, 1] -> Conv2D(c1, kernel x kernel, valid, relu) -> AveragePooling2D(2 x 2)
  *     -> Conv2D(c2, kernel x kernel, valid, relu) -> AveragePooling2D(2 x 2) -> Flatten (NHWC)
@@ -692,6 +692,48 @@ CFA_API int cfa_lenet_eval_f32(const float* x, size_t x_dev_stride, const int32_
                                const float* models, size_t pitch, int D, int batch, int batches,
                                const int32_t* skip, double target, int32_t* ended,
                                double* cost, double* cost_log, int log_cap, unsigned long long* epoch,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
+/* (TF2 drivers) A minibatch's loss and gradient for every device of a LeNet-1 population, the
+ * model family, row layout and geometry of the block above: the local update's
+ *   loss = reduce_mean(-sum(onehot * log(model(x)))); grads = tape.gradient(loss, weights)
+ * (..._MNIST_crossentropy_gradients_exchange.py:321-337), and the gradient a device evaluates at a
+ * neighbour's model on a batch of its own data (:360-385). The optimizer step is cfa_optim_step_f32.
+ *   x, labels, Nt, strides: the training set, shared (strides 0) or one per device, as above.
+ *   models  [D, pitch] fp32, pitch >= P, read only.
+ *   src     [D] int32 DEVICE array or NULL: device d evaluates row src[d] of models on its OWN
+ *           data (:360-385); NULL: row d. A value outside [0, D) is the caller's error (nothing is
+ *           read through it; that device's row and loss become NaN).
+ *   first   [D] int64 DEVICE array or NULL: the index of the first sample of device d's batch
+ *           (NULL: 0), on the device so that a captured epoch can advance it. Sample s of the batch
+ *           is sample (first[d] + s) mod Nt of the set: a batch past the set's end wraps.
+ *   skip    [D] int32 or NULL: a flagged device does no work; its grads row and loss are untouched.
+ *   grads   [D, gpitch] fp32, gpitch >= P, any alignment; elements P.. of a row are not written.
+ *   loss    [D] fp32 or NULL: the batch's mean loss.
+ * For every other device, per sample with label l and logits z (fp32, explicit fma, fixed order):
+ *   dz[c] = exp(z_c - max) / sum - (c == l); dWd = flat (x) dz; dbd = dz; dflat = Wd dz;
+ *   average pool backward: 0.25 d(pooled) to each window position, 0 to a dropped row or column;
+ *   relu gate z > 0 (the forward's own test); dK[ky][kx][ci][co] = sum_{y,x} in[y+ky][x+kx][ci] dzc[y][x][co];
+ *   db[co] = sum_{y,x} dzc[y][x][co]; stage 2's input gradient the transposed correlation.
+ *   grads[d] = (sum over the batch) / batch, loss[d] = (sum of the samples' losses, in order) / batch,
+ * the loss bit for bit the batch loss of cfa_lenet_eval_f32 on the same samples.
+ * Deterministic, no atomics: the batch is cut into groups of 4 samples whatever D, skip, src or the
+ * GPU are, a group's sums have a fixed order and the groups are added in order, so a device's row
+ * has the same bits alone or in a population. A label outside [0, classes) reads nothing out of
+ * bounds and makes that device's loss and whole row NaN. workspace: at least
+ * cfa_lenet_grad_workspace_bytes(D, batch, geometry) bytes of DEVICE memory (0 for D or batch < 1
+ * or a geometry without a model). No host read, allocation or attribute call after
+ * cfa_device_prepare: capture-safe. Two launches.
+ * CFA_E_INVALID: a null x, labels, models, grads or workspace; D, batch or Nt < 1; a bad geometry;
+ * batch > Nt; pitch or gpitch < P; a non-zero device stride below one device's set; a workspace
+ * too small. CFA_E_UNSUPPORTED: classes > 64, D > 65535, or a model, its gradient and two
+ * samples' activations beyond one workgroup's LDS, e.g. (28, 3, 32, 64, 10): refused. */
+CFA_API size_t cfa_lenet_grad_workspace_bytes(int D, int batch, int side, int kernel, int c1, int c2, int classes);
+CFA_API int cfa_lenet_grad_f32(const float* x, size_t x_dev_stride, const int32_t* labels, size_t label_dev_stride,
+                               int Nt, int side, int kernel, int c1, int c2, int classes,
+                               const float* models, size_t pitch, int D, const int32_t* src,
+                               const long long* first, int batch, const int32_t* skip,
+                               float* grads, size_t gpitch, float* loss,
                                void* workspace, size_t workspace_bytes, void* stream);
 
 /* (a1-a6 batched) Population round: one launch mixes D devices.
