@@ -9,10 +9,16 @@ AveragePooling2D; Flatten in NHWC order; Dense(classes, softmax). A model row is
 order, C-order: K1 b1 K2 b2 Wd bd.
 
 Data: images rng.random in [0, 1), weights 0.1 * standard_normal, labels uniform. With it every
-class probability stays above 0.07 and the costs lie between 1 and 2.4, far from the region where
-a probability underflows in fp32 (there the library's log-softmax and the reference's log of the
-softmax differ by design), and an fp32 evaluation differs from this fp64 one by about 6e-8
-normwise: conftest.normwise_close at 1e-5 has more than 100x of margin."""
+class probability stays above 0.07 (above 0.014 in the PATHS cases, which have up to 40 classes)
+and the costs lie between 1 and 2.4 (up to 3.9 there), far from the region where a probability
+underflows in fp32 (there the library's log-softmax and the reference's log of the softmax differ
+by design; tests/test_gpu_lenet_paths.py goes there on purpose, with a model of its own), and an
+fp32 evaluation differs from this fp64 one by about 6e-8 normwise: conftest.normwise_close at 1e-5
+has more than 100x of margin.
+
+PATHS names the cases that exist for a loop or branch of cfa_lenet.hip the others never take;
+`path(name, ...)` restates the launch plan (cfa_lenet.hip, cfa_internal.h: shared_grid_x) and
+gives the arithmetic that puts the case there, as named conditions that the tests assert."""
 import numpy as np
 
 LENET1 = (28, 5, 4, 8, 10)
@@ -23,8 +29,21 @@ CASES = {
     "pool2_drops": ((12, 3, 2, 3, 4), 3, 2, 7),   # conv2 output 3: the second pool drops a row and column; P = 93
     "pool1_drops": ((14, 4, 3, 5, 3), 3, 2, 7),   # conv1 output 11: the first pool drops a row and column
     "map_1x1": ((13, 4, 3, 5, 3), 3, 2, 7),       # flat = 5: a 1 x 1 map
+    # the paths no case above takes (PATHS, path()), each again with one unused tail sample
+    "many_batches": ((12, 3, 2, 3, 4), 3, 5, 16),    # at D = 600: 2 workgroups own a device's 5 batches, D > 256
+    "chunk_tail_1": ((12, 3, 2, 3, 4), 5, 2, 11),    # chunks of 4 and 1 samples
+    "chunk_tail_2": ((12, 3, 2, 3, 4), 6, 2, 13),    # chunks of 4 and 2 samples
+    "k5_drops": ((23, 5, 4, 13, 17), 5, 2, 11),      # 23 -> 19 -> 9 -> 5 -> 2: the K = 5 kernel, both pools drop
+    "raised_lds": ((20, 3, 8, 32, 40), 3, 1, 4),     # P = 13 976: 77 932 bytes of LDS, above the default 64 KiB
 }
+PATHS = ("many_batches", "chunk_tail_1", "chunk_tail_2", "k5_drops", "raised_lds")
+MANY_D = 600  # the population of "many_batches"
 UNSUPPORTED = (28, 3, 32, 64, 10)  # P = 34 826: beyond one workgroup's LDS
+
+
+# cfa_lenet.hip: kLenetBlock, kLenetChunk, the workgroups per CU of the launch; the dynamic LDS of a
+# launch before the kernel's limit is raised
+BLOCK, CHUNK, WG_PER_CU, LDS_DEFAULT = 256, 4, 4, 65536
 
 
 def stages(geom):
@@ -55,6 +74,47 @@ def split(row, geom):
         o += n
     assert o == len(row)
     return out
+
+
+def eval_lds_bytes(geom, batch):
+    """lenet_eval_lds: the model, a chunk's activations (image, two pooled maps, logits), a batch's losses."""
+    side, k, c1, c2, classes = geom
+    _, p1, _, p2 = stages(geom)
+    sample = side * side + p1 * p1 * c1 + p2 * p2 * c2 + classes
+    return 4 * (size(geom) + CHUNK * sample + batch)
+
+
+def eval_grid_x(batches, D, cus):
+    """grid.x of lenet_eval_kernel: shared_grid_x(batches, 4, D) workgroups per device, evened out."""
+    gx = max(1, min(batches, (cus * WG_PER_CU + D - 1) // D))
+    per = (batches + gx - 1) // gx
+    return (batches + per - 1) // per
+
+
+def path(name, D=1, cus=256, lds_limit=160 * 1024):
+    """The conditions that put the PATHS case `name` on its path, {text: bool}, for a population of
+    D on a device of `cus` compute units and `lds_limit` bytes of LDS per workgroup."""
+    geom, batch, batches, Nt = CASES[name]
+    side, k, c1, c2, classes = geom
+    s1, p1, s2, p2 = stages(geom)
+    tail = batch % CHUNK
+    if name == "many_batches":
+        gx = eval_grid_x(batches, D, cus)
+        return {"fewer workgroups than batches: ceil(4 CUs / D) < batches": (WG_PER_CU * cus + D - 1) // D < batches,
+                "a workgroup's batch loop runs again": 1 <= gx < batches,
+                "the finish kernel's device loop runs again": D > BLOCK}
+    if name in ("chunk_tail_1", "chunk_tail_2"):
+        return {"a full chunk, then one of %d" % tail: batch > CHUNK and tail == int(name[-1])}
+    if name == "k5_drops":
+        return {"the K = 5 kernel": k == 5, "both pools drop a row and column": s1 % 2 == 1 and s2 % 2 == 1,
+                "a third, partial-wave pass of lenet_logits: 4 * 17 * 8 = 544 = 2 * 256 + 32":
+                    CHUNK * classes * 8 == 544 and 0 < CHUNK * classes * 8 % BLOCK < 64,
+                "a chunk of one sample": tail == 1}
+    if name == "raised_lds":
+        need = eval_lds_bytes(geom, batch)
+        return {"77 932 bytes of LDS": need == 77932, "above the default limit": need > LDS_DEFAULT,
+                "within the device's": need <= lds_limit}
+    raise KeyError(name)
 
 
 def conv_valid(h, K, b):

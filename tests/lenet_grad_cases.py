@@ -13,7 +13,15 @@ term, far above the 1e-5 tolerance, so a case's seed is chosen (here, from the r
 such that over EVERY model and EVERY sample of its set the smallest |pre-activation| of both
 convolutions stays above 1e-5 of the largest (`margin`); an fp32 evaluation moves a
 pre-activation by about 3e-7 of the largest (test_lenet_training_host.py holds it to a tenth of
-the margin). Whatever batch, `first`, `src` or per-device set a test picks stays inside that."""
+the margin). Whatever batch, `first`, `src` or per-device set a test picks stays inside that.
+
+PATHS names the cases that exist for a loop, a lane plan or a branch of cfa_lenet_grad.hip and
+cfa_lenet_graph.h the others never take. `plan` restates the launch plan from the geometry and the
+batch alone, and `path` gives the arithmetic that puts a case on its path as named conditions that
+the tests assert. A PATHS case's seed is the smallest that meets the margin rule and under which no
+model has a tensor whose gradient is all zero on any batch of the set (with one or two channels a
+model's relus are often all shut, and a comparison relative to a zero tensor says nothing);
+test_lenet_training_host.py derives it again."""
 import numpy as np
 
 import lenet_cases as lc
@@ -27,8 +35,90 @@ CASES = {
     "pool1_drops": ((14, 4, 3, 5, 3), 3, 7, 0),    # the first pool drops a row and column
     "map_1x1": ((13, 4, 3, 5, 3), 3, 7, 0),        # a 1 x 1 final map
     "generic_k": ((16, 3, 3, 4, 5), 5, 11, 1),     # the runtime-k kernel, two groups, the second a partial chunk
+    # the paths no case above takes (PATHS, path()); a seed is the smallest that meets the margin rule and
+    # leaves no tensor's gradient all zero (a model whose relus are all shut: seeds 0 to 33 of lanes_64)
+    "k5_drops": ((23, 5, 4, 13, 17), 9, 13, 1),       # 23 -> 19 -> 9 -> 5 -> 2: the K = 5 kernel where both pools
+                                                      # drop, 260 items, 272 logit lanes, groups of 4, 4 and 1
+    "generic_items": ((12, 3, 8, 11, 4), 3, 7, 1),    # the runtime-k kernel with 264 items
+    "lanes_64": ((10, 3, 1, 1, 2), 3, 7, 34),         # 3 items, 1 channel: 64 lanes a sum, fewer rows than lanes
+    "classes_64": ((12, 3, 2, 3, 64), 3, 7, 0),       # the entry's most classes: 1 024 logit lanes
+    "classes_33": ((12, 3, 2, 3, 33), 3, 7, 1),       # 528 logit lanes: a third pass of 16
+    "finish_255": ((10, 3, 4, 5, 5), 3, 7, 0),        # P + 1 = 256: the loss is the finish block's last thread
+    "finish_256": ((14, 3, 4, 4, 4), 3, 7, 2),        # P + 1 = 257: a second finish block of one live thread
+    "raised_lds": ((20, 3, 8, 32, 40), 3, 4, 1),      # P = 13 976: 141 736 bytes of LDS, above the default 64 KiB
 }
+PATHS = ("k5_drops", "generic_items", "lanes_64", "classes_64", "classes_33", "finish_255", "finish_256",
+         "raised_lds")
 GUARD = 1e-5
+# cfa_lenet_grad.hip: kGradBlockL, kGradChunk, kGradGroup
+BLOCK, CHUNK, GROUP = 256, 2, 4
+
+
+def lanes(items, T=BLOCK):
+    """lenet_lanes: the lanes that share one of `items` sums."""
+    L = 1
+    while L < 64 and 2 * L * items <= T:
+        L *= 2
+    return L
+
+
+def grad_lds_bytes(geom):
+    """lenet_grad_lds: model and gradient sums, a chunk's activations and their gradients, a group's
+    losses, a chunk's labels, the gate bytes."""
+    side, k, c1, c2, classes = geom
+    _, p1, _, p2 = lc.stages(geom)
+    n1, flat = p1 * p1 * c1, p2 * p2 * c2
+    sample = side * side + 2 * n1 + 2 * flat + 2 * classes + 4 * flat
+    return 4 * (2 * lc.size(geom) + CHUNK * sample + GROUP + CHUNK + (CHUNK * (n1 + flat) + 3) // 4)
+
+
+def plan(name):
+    """What the launch of a case looks like from the geometry and the batch alone: the kernel, the
+    items, lanes and rows (of a one-sample chunk) of both weight gradients, the lanes of both bias
+    gradients, the lanes of lenet_logits for a full chunk, the groups and the LDS."""
+    geom, batch, _, _ = CASES[name]
+    side, k, c1, c2, classes = geom
+    s1, p1, s2, p2 = lc.stages(geom)
+    groups = (batch + GROUP - 1) // GROUP
+    return {"fast": k == 5, "s": (s1, p1, s2, p2), "items": (k * c1, k * c1 * c2),
+            "L": (lanes(k * c1), lanes(k * c1 * c2)), "rows": (2 * p1, 2 * p2), "Lb": (lanes(c1), lanes(c2)),
+            "logit_lanes": min(CHUNK, batch) * classes * 8, "groups": groups, "last": batch - GROUP * (groups - 1),
+            "lds": grad_lds_bytes(geom), "finish_blocks": (lc.size(geom) + 1 + BLOCK - 1) // BLOCK}
+
+
+def path(name, lds_limit=160 * 1024):
+    """The conditions that put the PATHS case `name` on its path, {text: bool}; `lds_limit` is the
+    device's LDS per workgroup."""
+    p, P = plan(name), lc.size(CASES[name][0])
+    if name == "k5_drops":
+        return {"the K = 5 kernel": p["fast"],
+                "both pools drop a row and column": p["s"][0] % 2 == 1 and p["s"][2] % 2 == 1,
+                "stage 2: 5 * 4 * 13 = 260 items > 256, one lane each, a second pass of `idx += T`":
+                    p["items"][1] == 260 > BLOCK and p["L"][1] == 1,
+                "lenet_logits: 2 * 17 * 8 = 272 lanes > 256, a second pass of 16": p["logit_lanes"] == 272,
+                "three groups, the last of one sample": (p["groups"], p["last"]) == (3, 1), "P = 2 318": P == 2318}
+    if name == "generic_items":
+        return {"the runtime-k kernel": not p["fast"],
+                "stage 2: 3 * 8 * 11 = 264 items > 256, one lane each, a second pass":
+                    p["items"][1] == 264 > BLOCK and p["L"][1] == 1}
+    if name == "lanes_64":
+        return {"3 items per stage: 64 lanes a sum": p["items"] == (3, 3) and p["L"] == (64, 64),
+                "one channel per stage: 64 lanes a bias sum": p["Lb"] == (64, 64),
+                "a one-sample chunk has 8 and 2 rows, a full one 16 and 4: lanes without a row": p["rows"] == (8, 2),
+                "a one-sample chunk occurs": CASES[name][1] % CHUNK == 1}
+    if name in ("classes_64", "classes_33"):
+        C = CASES[name][0][4]
+        last = 16 * C % BLOCK or BLOCK
+        return {"lenet_logits: 2 * C * 8 = %d lanes, passes of 256 and a last one of %d" % (16 * C, last):
+                    p["logit_lanes"] == 16 * C > BLOCK,
+                "the entry's most classes, or a last pass below a wave": C == 64 or last < 64}
+    if name in ("finish_255", "finish_256"):
+        return {"P + 1 = %d: %d finish blocks" % (P + 1, p["finish_blocks"]):
+                    (P + 1, p["finish_blocks"]) == ((256, 1) if name == "finish_255" else (257, 2))}
+    if name == "raised_lds":
+        return {"141 736 bytes of LDS": p["lds"] == 141736, "above the default limit": p["lds"] > lc.LDS_DEFAULT,
+                "within the device's": p["lds"] <= lds_limit}
+    raise KeyError(name)
 
 
 def _conv32(h, K, b):
@@ -104,6 +194,21 @@ def preactivation_shift(x, row, geom):
     _, a1, _, a2, _ = _forward(x, row, geom)
     _, b1, _, b2, _ = _forward(x, row, geom, np.float32)
     return float(max(np.abs(a1 - b1).max(), np.abs(a2 - b2).max()))
+
+
+def meets_the_seed_rule(geom, batch, Nt, seed):
+    """A PATHS case's rule for a seed: the margin rule over every model and sample of the set, and no
+    tensor's gradient all zero for any model on any batch of the set."""
+    x, labels, models = lc.make(geom, D, Nt, seed)
+    for row in models:
+        lo, hi = margin(x, row, geom)
+        if not (lo >= GUARD * hi and preactivation_shift(x, row, geom) <= 0.1 * lo):
+            return False
+        for first in range(Nt):
+            idx = (np.arange(batch) + first) % Nt
+            if not all(np.abs(t).max() > 0 for t in tensors(grads(x[idx], labels[idx], row, geom)[0], geom)):
+                return False
+    return True
 
 
 def tensors(vec, geom):

@@ -56,6 +56,35 @@ def test_no_relu_gate_is_within_rounding_of_its_threshold(name):
         assert shift <= 0.1 * lo
 
 
+@pytest.mark.parametrize("name", gc.PATHS)
+def test_a_path_case_reaches_its_path_with_the_smallest_seed_that_meets_the_rule(name):
+    """The arithmetic of gc.path (items against 256 lanes, logit lanes against 256, P + 1 against a
+    finish block, LDS bytes against 64 KiB) from the mirror of the launch plan, and the seed derived
+    again from the restatement alone: no smaller one meets the margin rule with every tensor's
+    gradient non-zero on every batch of the set."""
+    conditions = gc.path(name)
+    print(name, gc.plan(name))
+    assert conditions and all(conditions.values()), [k for k, v in conditions.items() if not v]
+    geom, batch, Nt, seed = gc.CASES[name]
+    assert [s for s in range(seed + 1) if gc.meets_the_seed_rule(geom, batch, Nt, s)] == [seed]
+    assert int(_lib.load().cfa_lenet_params(*geom)) == lc.size(geom) == lenet_size(geom)
+
+
+def test_the_lane_plans_of_the_cases():
+    """lenet_lanes over the table: the earlier cases reach 1 to 32 lanes a weight-gradient sum, never
+    more items than threads; the PATHS cases add 64 lanes (fewer rows than lanes) and one lane with
+    more items than threads, a second pass of lenet_logits, a third group and LDS above 64 KiB."""
+    assert [gc.lanes(n) for n in (1, 4, 5, 8, 9, 20, 36, 128, 129, 256, 257)] == [64, 64, 32, 32, 16, 8, 4, 2, 1, 1, 1]
+    before = {L for n in gc.CASES if n not in gc.PATHS for L in gc.plan(n)["L"]}
+    assert before == {32, 16, 8, 4, 1} and gc.plan("lenet1")["L"] == (8, 1) and gc.plan("generic_k")["L"] == (16, 4)
+    assert max(i for n in gc.CASES if n not in gc.PATHS for i in gc.plan(n)["items"]) <= gc.BLOCK
+    assert max(gc.plan(n)["logit_lanes"] for n in gc.CASES if n not in gc.PATHS) <= gc.BLOCK
+    assert max(gc.plan(n)["groups"] for n in gc.CASES if n not in gc.PATHS) == 2
+    assert all(gc.plan(n)["lds"] <= lc.LDS_DEFAULT for n in gc.CASES if n != "raised_lds")
+    # cfa_lenet_graph.h's 39.9 KiB: 2 * 2 202 + 2 * (784 + 1 152 + 256 + 20 + 512) + 4 + 2 + 352 floats
+    assert gc.plan("lenet1")["lds"] == 4 * 10210 == 40840
+
+
 def test_check_returns_the_plan():
     info = LenetTraining.check(LENET1, (60000, 28, 28), (60000,), 100)
     assert (info["P"], info["Nt"], info["batch"], info["per_device"]) == (2202, 60000, 100, 0)

@@ -97,6 +97,26 @@ def test_restatement_against_torch_cpu_fp64(name):
     assert normwise_close(ref, got, 1e-10)
 
 
+def test_a_path_case_reaches_its_path():
+    """The arithmetic of lc.path from the mirror of the launch plan: workgroups against batches for
+    any device of up to 300 compute units, chunk tails, logit lanes against 256, LDS bytes against
+    64 KiB; and that no earlier case is there."""
+    for name in lc.PATHS:
+        for cus in (1, 104, 256, 300):
+            conditions = lc.path(name, lc.MANY_D, cus)
+            assert conditions and all(conditions.values()), (name, cus, [k for k, v in conditions.items() if not v])
+    assert lc.eval_grid_x(5, lc.MANY_D, 256) == 2  # batches 0, 2, 4 and 1, 3
+    assert lc.eval_grid_x(100, 30, 256) == 34      # docs/history.md: 34 groups of 3 batches
+    for name, (geom, batch, batches, _) in lc.CASES.items():
+        if name not in lc.PATHS:
+            assert lc.eval_grid_x(batches, 5, 104) == batches   # one batch per workgroup at the tests' D <= 5
+            assert lc.eval_lds_bytes(geom, batch) <= lc.LDS_DEFAULT
+            s1, _, s2, _ = lc.stages(geom)
+            assert batch % lc.CHUNK in (0, 3) and (geom[1] != 5 or s1 % 2 == s2 % 2 == 0)
+    assert lc.eval_lds_bytes(lc.LENET1, 100) == 4 * (2202 + 4 * (784 + 576 + 128 + 10) + 100)  # 33 KB
+    assert lc.eval_lds_bytes(lc.UNSUPPORTED, 2) > 160 * 1024
+
+
 def test_flag_rule_of_the_restatement():
     cost = np.array([0.4, 0.6, 0.2, 0.7])
     assert lc.flags(cost, 0.5).tolist() == [1, 0, 1, 0]
