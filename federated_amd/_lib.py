@@ -38,6 +38,15 @@ CLIENT_NONE, CLIENT_COPY, CLIENT_MIX = 0, 1, 2  # cfa_fedavg_population_round_f3
 FA_INIT, FA_ROUND = 0, 1  # cfa_fa_population_round_f32 modes
 ENDED_COPY, ENDED_TRUNCATE, ENDED_TRUNCATE_EPS = 0, 1, 2  # cfa_mix_population_ended_f32 rules
 OPTIM_SGD, OPTIM_MOMENTUM, OPTIM_ADAM = 0, 1, 2  # cfa_optim_step_f32 rules
+LENET_LOSS_XENT, LENET_LOSS_HUBER = 0, 1  # cfa_lenet_eval_loss_f32 / cfa_lenet_grad_loss_f32 objectives
+LENET_LOSSES = {"xent": LENET_LOSS_XENT, "huber": LENET_LOSS_HUBER}
+
+
+def lenet_loss_kind(loss) -> int:
+    """CFA_LENET_LOSS_* of a loss name ("xent" or "huber"); ValueError for anything else."""
+    if not isinstance(loss, str) or loss not in LENET_LOSSES:
+        raise ValueError(f"loss must be one of {sorted(LENET_LOSSES)}, got {loss!r}")
+    return LENET_LOSSES[loss]
 
 COMPRESS_NONE = 0
 COMPRESS_SPARSE = 1
@@ -150,10 +159,18 @@ SIGNATURES = {
                                     _c_int, _c_void_p, _c_size_t, _c_int, _c_int, _c_int, _c_void_p, ctypes.c_double,
                                     _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_size_t,
                                     _c_void_p]),
+    "cfa_lenet_eval_loss_f32": (_c_int, [_c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_int, _c_int, _c_int, _c_int,
+                                         _c_int, _c_int, _c_void_p, _c_size_t, _c_int, _c_int, _c_int, _c_void_p,
+                                         ctypes.c_double, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p,
+                                         _c_void_p, _c_size_t, _c_int, _c_void_p]),
     "cfa_lenet_grad_workspace_bytes": (_c_size_t, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int]),
     "cfa_lenet_grad_f32": (_c_int, [_c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_int, _c_int, _c_int, _c_int, _c_int,
                                     _c_int, _c_void_p, _c_size_t, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p,
                                     _c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "cfa_lenet_grad_loss_f32": (_c_int, [_c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_int, _c_int, _c_int, _c_int,
+                                         _c_int, _c_int, _c_void_p, _c_size_t, _c_int, _c_void_p, _c_void_p, _c_int,
+                                         _c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_int,
+                                         _c_void_p]),
     "cfa_optim_tile": (_c_int, []),
     "cfa_optim_workspace_bytes": (_c_size_t, [_c_int, _c_size_t, _c_int]),
     "cfa_optim_step_f32": (_c_int, [_c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t,

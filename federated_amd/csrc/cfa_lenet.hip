@@ -2,6 +2,8 @@
 // over the test set in batches, the mean batch loss and the training_end flag it raises
 // (federated_learning_keras_consensus_FL_threads_MNIST_crossentropy_gradients_exchange.py:430-455,
 // the model of :158-194), on the forward phases of cfa_lenet_graph.h. Forward only: the gradient is cfa_lenet_grad.hip.
+// The loss phase is the cross-entropy drivers' or the Huber drivers'
+// (federated_learning_keras_consensus_FL_MNIST.py:481-483), a template parameter of the kernel.
 //
 // Launch 1, grid (batch groups, D): a workgroup stages its device's model into LDS once and owns
 // whole batches b = blockIdx.x, blockIdx.x + gridDim.x, ... A batch goes through the phases in
@@ -34,7 +36,8 @@ inline long long lenet_eval_lds(const LenetGeom& g, int batch) {
   return g.P + (long long)kLenetChunk * lenet_sample_floats(g) + batch;
 }
 
-template <int K>
+// K: the kernel side at compile time, or 0; LOSS: the objective (CFA_LENET_LOSS_*).
+template <int K, int LOSS>
 __global__ __launch_bounds__(kLenetBlock) void lenet_eval_kernel(LenetArgs a, LenetGeom g) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int dv = blockIdx.y;
@@ -63,7 +66,7 @@ __global__ __launch_bounds__(kLenetBlock) void lenet_eval_kernel(LenetArgs a, Le
       __syncthreads();
       lenet_logits(zl, a2, m + g.oWd, m + g.obd, ns, g.flat, g.C, tid, T);
       __syncthreads();
-      lenet_xent(loss + s0, zl, ld + first + s0, ns, g.C, tid, T);
+      lenet_loss<LOSS>(loss + s0, zl, ld + first + s0, ns, g.C, tid, T);
     }
     __syncthreads();
     if (tid == 0) {  // reduce_mean over the batch, fp32, in sample order
@@ -117,6 +120,15 @@ __global__ __launch_bounds__(kLenetBlock) void lenet_finish_kernel(LenetFinish f
 // The kernel side the evaluation kernel is instantiated for: LeNet-1's 5, every other one 0.
 inline bool lenet_fast(const LenetGeom& g) { return g.k == 5; }
 
+using LenetEvalKernel = void (*)(LenetArgs, LenetGeom);
+
+// The instantiation for a geometry and an objective (a valid CFA_LENET_LOSS_*).
+inline LenetEvalKernel lenet_eval_kernel_for(bool fast, int loss) {
+  if (loss == CFA_LENET_LOSS_HUBER)
+    return fast ? lenet_eval_kernel<5, CFA_LENET_LOSS_HUBER> : lenet_eval_kernel<0, CFA_LENET_LOSS_HUBER>;
+  return fast ? lenet_eval_kernel<5, CFA_LENET_LOSS_XENT> : lenet_eval_kernel<0, CFA_LENET_LOSS_XENT>;
+}
+
 }  // namespace
 
 // Current device: raise the evaluation kernels' dynamic-LDS limit now (cfa_device_prepare), so
@@ -124,8 +136,9 @@ inline bool lenet_fast(const LenetGeom& g) { return g.k == 5; }
 int lenet_prepare_device() {
   const int lim = device_lds_max();
   if (lim <= 65536) return CFA_OK;  // nor would the gradient kernels' be raised
-  const void* kernels[] = {(const void*)lenet_eval_kernel<5>, (const void*)lenet_eval_kernel<0>};
-  for (const void* k : kernels) (void)raise_lds_limit(k, lim);  // refused: launches stay within 64 KiB
+  for (int loss : {CFA_LENET_LOSS_XENT, CFA_LENET_LOSS_HUBER})
+    for (bool fast : {true, false})  // refused: launches stay within 64 KiB
+      (void)raise_lds_limit((const void*)lenet_eval_kernel_for(fast, loss), lim);
   return lenet_grad_prepare_device();
 }
 
@@ -143,7 +156,21 @@ extern "C" int cfa_lenet_eval_f32(const float* x, size_t x_dev_stride, const int
                                   size_t pitch, int D, int batch, int batches, const int32_t* skip, double target,
                                   int32_t* ended, double* cost, double* cost_log, int log_cap,
                                   unsigned long long* epoch, void* workspace, size_t workspace_bytes, void* stream) {
-  const char* fn = "cfa_lenet_eval_f32";
+  return cfa_lenet_eval_loss_f32(x, x_dev_stride, labels, label_dev_stride, Nt, side, kernel, c1, c2, classes, models,
+                                 pitch, D, batch, batches, skip, target, ended, cost, cost_log, log_cap, epoch,
+                                 workspace, workspace_bytes, CFA_LENET_LOSS_XENT, stream);
+}
+
+extern "C" int cfa_lenet_eval_loss_f32(const float* x, size_t x_dev_stride, const int32_t* labels,
+                                       size_t label_dev_stride, int Nt, int side, int kernel, int c1, int c2,
+                                       int classes, const float* models, size_t pitch, int D, int batch, int batches,
+                                       const int32_t* skip, double target, int32_t* ended, double* cost,
+                                       double* cost_log, int log_cap, unsigned long long* epoch, void* workspace,
+                                       size_t workspace_bytes, int loss, void* stream) {
+  // the messages keep the name callers of either entry know
+  const char* fn = loss == CFA_LENET_LOSS_XENT ? "cfa_lenet_eval_f32" : "cfa_lenet_eval_loss_f32";
+  if (loss != CFA_LENET_LOSS_XENT && loss != CFA_LENET_LOSS_HUBER)
+    return fail(CFA_E_INVALID, "%s: unknown loss kind %d (CFA_LENET_LOSS_XENT or CFA_LENET_LOSS_HUBER)", fn, loss);
   if (!x || !labels || !models || !cost || !workspace) return fail(CFA_E_INVALID, "%s: null buffer", fn);
   if (D < 1 || batch < 1 || batches < 1 || Nt < 1)
     return fail(CFA_E_INVALID, "%s: D %d, batch %d, batches %d and Nt %d must be >= 1", fn, D, batch, batches, Nt);
@@ -171,9 +198,9 @@ extern "C" int cfa_lenet_eval_f32(const float* x, size_t x_dev_stride, const int
   if (D > 65535) return fail(CFA_E_UNSUPPORTED, "%s: more than 65535 devices", fn);
   // the kernel indexes the model and the LDS with ints
   const bool fast = lenet_fast(g);
-  const void* kern = fast ? (const void*)lenet_eval_kernel<5> : (const void*)lenet_eval_kernel<0>;
+  const LenetEvalKernel kern = lenet_eval_kernel_for(fast, loss);
   const long long need = g.P > (1 << 20) ? -1 : 4 * lenet_eval_lds(g, batch), limit = device_lds_max();
-  if (need < 0 || need > limit || (need > 65536 && !raise_lds_limit(kern, (int)limit)))
+  if (need < 0 || need > limit || (need > 65536 && !raise_lds_limit((const void*)kern, (int)limit)))
     return fail(CFA_E_UNSUPPORTED, "%s: a model of %lld parameters, %d samples' activations and a batch of %d losses "
                 "do not fit one workgroup's LDS", fn, g.P, kLenetChunk, batch);
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -183,10 +210,7 @@ extern "C" int cfa_lenet_eval_f32(const float* x, size_t x_dev_stride, const int
   // batches (but the last)
   const int per = (batches + (int)shared_grid_x(batches, 4, D) - 1) / (int)shared_grid_x(batches, 4, D);
   const dim3 grid((unsigned)((batches + per - 1) / per), (unsigned)D);
-  if (fast)
-    lenet_eval_kernel<5><<<grid, kLenetBlock, (size_t)need, st>>>(a, g);
-  else
-    lenet_eval_kernel<0><<<grid, kLenetBlock, (size_t)need, st>>>(a, g);
+  kern<<<grid, kLenetBlock, (size_t)need, st>>>(a, g);
   if (int rc = check_launch("lenet_eval_kernel")) return rc;
   const LenetFinish f{a.ws, D, batches, skip, target, ended, cost, cost_log, log_cap, epoch};
   lenet_finish_kernel<<<1, kLenetBlock, 0, st>>>(f);

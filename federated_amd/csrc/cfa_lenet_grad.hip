@@ -2,7 +2,9 @@
 // loss and tape.gradient of a local batch
 // (federated_learning_keras_consensus_FL_threads_MNIST_crossentropy_gradients_exchange.py:321-337)
 // and of a batch of a device's own data at a neighbour's model (:360-385), on the forward and
-// backward phases of cfa_lenet_graph.h.
+// backward phases of cfa_lenet_graph.h. The loss phase is the cross-entropy drivers' or the Huber
+// drivers' (federated_learning_keras_consensus_FL_MNIST.py:369-377), a template parameter of the
+// kernel; everything behind the gradient at the logits is shared.
 //
 // Launch 1, grid (sample groups, D): a batch's samples are cut into groups of kGradGroup, group g
 // owning samples [g * kGradGroup, ...) of the batch whatever D, the CU count, skip or src are. A
@@ -41,7 +43,8 @@ inline long long lenet_grad_lds(const LenetGeom& g) {
   return 2 * g.P + kGradChunk * sample + kGradGroup + kGradChunk + (kGradChunk * (n1 + g.flat) + 3) / 4;
 }
 
-template <int K>
+// K: the kernel side at compile time, or 0; LOSS: the objective (CFA_LENET_LOSS_*).
+template <int K, int LOSS>
 __global__ __launch_bounds__(kGradBlockL, 3) void lenet_grad_kernel(LenetGradArgs a, LenetGeom g) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int dv = blockIdx.y;
@@ -90,7 +93,7 @@ __global__ __launch_bounds__(kGradBlockL, 3) void lenet_grad_kernel(LenetGradArg
     __syncthreads();
     lenet_logits(zl, a2, m + g.oWd, m + g.obd, ns, g.flat, g.C, tid, T);
     __syncthreads();
-    lenet_xent(loss + c0, zl, lab, ns, g.C, tid, T, dzl);
+    lenet_loss<LOSS>(loss + c0, zl, lab, ns, g.C, tid, T, dzl);
     __syncthreads();
     lenet_dense_backward(gs + g.oWd, gs + g.obd, da2, a2, dzl, m + g.oWd, ns, g.flat, g.C, tid, T);
     __syncthreads();
@@ -138,14 +141,24 @@ __global__ __launch_bounds__(kGradBlockL) void lenet_grad_finish_kernel(LenetGra
 
 inline int lenet_grad_groups(int batch) { return (batch + kGradGroup - 1) / kGradGroup; }
 
+using LenetGradKernel = void (*)(LenetGradArgs, LenetGeom);
+
+// The instantiation for a geometry and an objective (a valid CFA_LENET_LOSS_*).
+inline LenetGradKernel lenet_grad_kernel_for(bool fast, int loss) {
+  if (loss == CFA_LENET_LOSS_HUBER)
+    return fast ? lenet_grad_kernel<5, CFA_LENET_LOSS_HUBER> : lenet_grad_kernel<0, CFA_LENET_LOSS_HUBER>;
+  return fast ? lenet_grad_kernel<5, CFA_LENET_LOSS_XENT> : lenet_grad_kernel<0, CFA_LENET_LOSS_XENT>;
+}
+
 }  // namespace
 
 // Current device: raise the gradient kernels' dynamic-LDS limit now (lenet_prepare_device).
 int lenet_grad_prepare_device() {
   const int lim = device_lds_max();
   if (lim <= 65536) return CFA_OK;
-  const void* kernels[] = {(const void*)lenet_grad_kernel<5>, (const void*)lenet_grad_kernel<0>};
-  for (const void* k : kernels) (void)raise_lds_limit(k, lim);  // refused: launches stay within 64 KiB
+  for (int loss : {CFA_LENET_LOSS_XENT, CFA_LENET_LOSS_HUBER})
+    for (bool fast : {true, false})  // refused: launches stay within 64 KiB
+      (void)raise_lds_limit((const void*)lenet_grad_kernel_for(fast, loss), lim);
   return CFA_OK;
 }
 
@@ -160,7 +173,22 @@ extern "C" int cfa_lenet_grad_f32(const float* x, size_t x_dev_stride, const int
                                   size_t pitch, int D, const int32_t* src, const long long* first, int batch,
                                   const int32_t* skip, float* grads, size_t gpitch, float* loss, void* workspace,
                                   size_t workspace_bytes, void* stream) {
-  const char* fn = "cfa_lenet_grad_f32";
+  return cfa_lenet_grad_loss_f32(x, x_dev_stride, labels, label_dev_stride, Nt, side, kernel, c1, c2, classes, models,
+                                 pitch, D, src, first, batch, skip, grads, gpitch, loss, workspace, workspace_bytes,
+                                 CFA_LENET_LOSS_XENT, stream);
+}
+
+extern "C" int cfa_lenet_grad_loss_f32(const float* x, size_t x_dev_stride, const int32_t* labels,
+                                       size_t label_dev_stride, int Nt, int side, int kernel, int c1, int c2,
+                                       int classes, const float* models, size_t pitch, int D, const int32_t* src,
+                                       const long long* first, int batch, const int32_t* skip, float* grads,
+                                       size_t gpitch, float* loss, void* workspace, size_t workspace_bytes,
+                                       int loss_kind, void* stream) {
+  // the messages keep the name callers of either entry know
+  const char* fn = loss_kind == CFA_LENET_LOSS_XENT ? "cfa_lenet_grad_f32" : "cfa_lenet_grad_loss_f32";
+  if (loss_kind != CFA_LENET_LOSS_XENT && loss_kind != CFA_LENET_LOSS_HUBER)
+    return fail(CFA_E_INVALID, "%s: unknown loss kind %d (CFA_LENET_LOSS_XENT or CFA_LENET_LOSS_HUBER)", fn,
+                loss_kind);
   if (!x || !labels || !models || !grads || !workspace) return fail(CFA_E_INVALID, "%s: null buffer", fn);
   if (D < 1 || batch < 1 || Nt < 1)
     return fail(CFA_E_INVALID, "%s: D %d, batch %d and Nt %d must be >= 1", fn, D, batch, Nt);
@@ -182,9 +210,9 @@ extern "C" int cfa_lenet_grad_f32(const float* x, size_t x_dev_stride, const int
   if (D > 65535) return fail(CFA_E_UNSUPPORTED, "%s: more than 65535 devices", fn);
   // the kernel indexes the model and the LDS with ints
   const bool fast = g.k == 5;
-  const void* kern = fast ? (const void*)lenet_grad_kernel<5> : (const void*)lenet_grad_kernel<0>;
+  const LenetGradKernel kern = lenet_grad_kernel_for(fast, loss_kind);
   const long long need = g.P > (1 << 20) ? -1 : 4 * lenet_grad_lds(g), limit = device_lds_max();
-  if (need < 0 || need > limit || (need > 65536 && !raise_lds_limit(kern, (int)limit)))
+  if (need < 0 || need > limit || (need > 65536 && !raise_lds_limit((const void*)kern, (int)limit)))
     return fail(CFA_E_UNSUPPORTED, "%s: a model of %lld parameters, its gradient and %d samples' activations do not "
                 "fit one workgroup's LDS", fn, g.P, kGradChunk);
   const size_t ws_need = cfa_lenet_grad_workspace_bytes(D, batch, side, kernel, c1, c2, classes);
@@ -195,10 +223,7 @@ extern "C" int cfa_lenet_grad_f32(const float* x, size_t x_dev_stride, const int
   const LenetGradArgs a{x, labels, (long long)x_dev_stride, (long long)label_dev_stride, models, (long long)pitch,
                         src, first, skip, Nt, batch, D, groups, static_cast<float*>(workspace)};
   const dim3 grid((unsigned)groups, (unsigned)D);
-  if (fast)
-    lenet_grad_kernel<5><<<grid, kGradBlockL, (size_t)need, st>>>(a, g);
-  else
-    lenet_grad_kernel<0><<<grid, kGradBlockL, (size_t)need, st>>>(a, g);
+  kern<<<grid, kGradBlockL, (size_t)need, st>>>(a, g);
   if (int rc = check_launch("lenet_grad_kernel")) return rc;
   const LenetGradFinish f{a.ws, (int)g.P, groups, batch, skip, grads, (long long)gpitch, loss};
   const dim3 fgrid((unsigned)((g.P + 1 + kGradBlockL - 1) / kGradBlockL), (unsigned)D);

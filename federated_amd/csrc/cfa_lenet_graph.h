@@ -6,7 +6,8 @@
 // on the host.
 //   x [side, side, 1] -> Conv2D(c1, k x k, valid) + b1 -> relu -> AveragePooling2D(2 x 2, stride 2)
 //     -> Conv2D(c2, k x k, valid) + b2 -> relu -> AveragePooling2D(2 x 2) -> Flatten -> Dense(classes)
-//   loss = -log softmax(z)[label], evaluated as -(z_l - max - log(sum exp(z - max)))
+//   loss = -log softmax(z)[label], evaluated as -(z_l - max - log(sum exp(z - max))), or the Huber
+//   drivers' Huber(label, softmax(z)[label]) (lenet_huber); a kernel is instantiated for one of the two (lenet_loss)
 // Keras conventions kept: Conv2D is a cross-correlation with the kernel tensor (kh, kw, in, out);
 // activations are NHWC, so Flatten gives index (h * w + x) * c2 + c; "valid" pooling drops an odd
 // last row and column. A model row is get_weights() order, C-order: K1 b1 K2 b2 Wd bd.
@@ -21,7 +22,7 @@
 // which chunk, workgroup or device evaluates it. fp32 throughout. Not installed, not an ABI.
 //
 // Backward (per sample; the 1 / batch factor belongs to the caller's finishing step):
-//   dz[c] = exp(z_c - max) / sum - (c == l), with the forward's own max and sum
+//   dz[c] = exp(z_c - max) / sum - (c == l), with the forward's own max and sum (lenet_huber: its own)
 //   dWd[i][c] = flat[i] dz[c], dbd[c] = dz[c], dflat[i] = sum_c Wd[i][c] dz[c]
 //   pool: each of a window's four positions receives 0.25 d(pooled); a dropped row or column none
 //   relu: the forward's own test z > 0 (z == 0 passes nothing, as TF's ReluGrad)
@@ -170,6 +171,49 @@ __device__ __forceinline__ void lenet_xent(float* loss, const float* zl, const i
       for (int c = 0; c < C; ++c) dz[s * C + c] = ok ? expf(z[c] - mx) / sum - (c == l ? 1.f : 0.f) : NAN;
     }
   }
+}
+
+// The Huber drivers' objective (federated_learning_keras_consensus_FL_MNIST.py:369-377, validation
+// :481-483): keras.losses.Huber() (delta = 1) between the integer label itself, cast to float, and
+// the softmax probability of the true class. loss[s] = 0.5 e^2 where |e| <= 1, else |e| - 0.5, with
+// e = p - (float)l and p = exp(z_l - max) / sum, lenet_xent's own max, sum and quotient. Same
+// shape: one thread per sample, classes in order; a label outside [0, C) reads nothing and gives
+// NaN. dz (or null): [ns][C], (g p) ((c == l) - exp(z_c - max) / sum) with g = e on the quadratic
+// branch and sign(e) on the linear one; all NaN for such a label. With 0 < p < 1 the label alone
+// picks the branch (0: quadratic in p; 1: quadratic in 1 - p; 2 and above: linear); where p
+// rounds to exactly 0 or 1 in fp32, e of label 0 or 2 lands on a branch's edge, and <= keeps the
+// quadratic branch there, as Keras does.
+__device__ __forceinline__ void lenet_huber(float* loss, const float* zl, const int32_t* labels, int ns, int C,
+                                            int tid, int T, float* dz = nullptr) {
+  for (int s = tid; s < ns; s += T) {
+    const float* z = zl + s * C;
+    float mx = z[0];
+    for (int c = 1; c < C; ++c) mx = fmaxf(mx, z[c]);
+    float sum = 0.f;
+    for (int c = 0; c < C; ++c) sum += expf(z[c] - mx);
+    const int l = labels[s];
+    const bool ok = (unsigned)l < (unsigned)C;
+    const float p = ok ? expf(z[l] - mx) / sum : NAN;
+    const float e = p - (float)l, ae = fabsf(e);
+    const bool quad = ae <= 1.f;  // false for NaN: the linear branch keeps it NaN
+    loss[s] = quad ? 0.5f * e * e : ae - 0.5f;
+    if (dz) {
+      const float gp = (quad ? e : e > 0.f ? 1.f : -1.f) * p;
+      for (int c = 0; c < C; ++c) dz[s * C + c] = ok ? gp * ((c == l ? 1.f : 0.f) - expf(z[c] - mx) / sum) : NAN;
+    }
+  }
+}
+
+// The loss phase of a kernel instantiated for the objective LOSS (CFA_LENET_LOSS_XENT or
+// CFA_LENET_LOSS_HUBER; the entry points refuse any other): the cross-entropy kernels hold
+// lenet_xent alone, as they did before there was a second objective.
+template <int LOSS>
+__device__ __forceinline__ void lenet_loss(float* loss, const float* zl, const int32_t* labels, int ns, int C,
+                                           int tid, int T, float* dz = nullptr) {
+  if constexpr (LOSS == CFA_LENET_LOSS_HUBER)
+    lenet_huber(loss, zl, labels, ns, C, tid, T, dz);
+  else
+    lenet_xent(loss, zl, labels, ns, C, tid, T, dz);
 }
 
 // ---- backward phases --------------------------------------------------------------------------

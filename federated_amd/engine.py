@@ -567,8 +567,8 @@ class Engine:
                    batch: int, batches: int, cost: torch.Tensor, workspace: torch.Tensor,
                    skip: Optional[torch.Tensor] = None, target: float = 0.0, ended: Optional[torch.Tensor] = None,
                    cost_log: Optional[torch.Tensor] = None, epoch: Optional[torch.Tensor] = None,
-                   stream=None) -> torch.Tensor:
-        """cfa_lenet_eval_f32: the validation cost of every device of ``models`` [D, P] (fp32 CUDA,
+                   stream=None, loss: str = "xent") -> torch.Tensor:
+        """cfa_lenet_eval_loss_f32: the validation cost of every device of ``models`` [D, P] (fp32 CUDA,
         unit element stride, any row pitch, read only; get_weights() order) on the LeNet-family
         ``geom`` = (side, kernel, c1, c2, classes), over ``batches`` batches of ``batch`` samples
         of the test set ``x`` [Nt, side, side] fp32 / ``labels`` [Nt] int32 that all devices share,
@@ -577,8 +577,11 @@ class Engine:
         CUDA flags or None: a flagged device's cost and flag are not touched. ``ended`` [D] int32
         CUDA or None: ``ended[d] |= cost[d] < target``; it may be ``skip`` itself. ``cost_log``
         [cap, D] fp64 CUDA and ``epoch`` (one-element int64 CUDA counter), given together: as
-        ``local_sgd``. ``workspace``: ``lenet_workspace(D, batches)``. The library validates the
-        rest (CFAError)."""
+        ``local_sgd``. ``workspace``: ``lenet_workspace(D, batches)``. ``loss``: "xent" (the
+        cross-entropy drivers' objective) or "huber" (the Huber drivers': Huber(label,
+        softmax(z)[label])); ValueError for any other, before any device call. The library
+        validates the rest (CFAError)."""
+        kind = _lib.lenet_loss_kind(loss)
         geom = tuple(int(v) for v in geom)
         if len(geom) != 5:
             raise ValueError("geom must be (side, kernel, c1, c2, classes)")
@@ -618,12 +621,12 @@ class Engine:
         pitch = int(models.stride(0)) if D > 1 else P
         if pitch < P:
             raise ValueError("models rows overlap (pitch below P)")
-        _lib.call("cfa_lenet_eval_f32", x.data_ptr(), x_stride, labels.data_ptr(), label_stride, Nt, *geom,
+        _lib.call("cfa_lenet_eval_loss_f32", x.data_ptr(), x_stride, labels.data_ptr(), label_stride, Nt, *geom,
                   models.data_ptr(), pitch, D, batch, batches, skip.data_ptr() if skip is not None else None,
                   float(target), ended.data_ptr() if ended is not None else None, cost.data_ptr(),
                   cost_log.data_ptr() if cost_log is not None else None, cap,
                   epoch.data_ptr() if epoch is not None else None, workspace.data_ptr(), workspace.numel() * 4,
-                  self.stream_handle(stream))
+                  kind, self.stream_handle(stream))
         return cost
 
     # -- minibatch gradient of a TF2 LeNet-1 population ---------------------------------------
@@ -635,8 +638,8 @@ class Engine:
     def lenet_grad(self, geom: Sequence[int], x: torch.Tensor, labels: torch.Tensor, models: torch.Tensor,
                    batch: int, grads: torch.Tensor, workspace: torch.Tensor, loss: Optional[torch.Tensor] = None,
                    src: Optional[torch.Tensor] = None, first: Optional[torch.Tensor] = None,
-                   skip: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
-        """cfa_lenet_grad_f32: the mean loss and its gradient over one batch of ``batch`` samples
+                   skip: Optional[torch.Tensor] = None, stream=None, loss_kind: str = "xent") -> torch.Tensor:
+        """cfa_lenet_grad_loss_f32: the mean loss and its gradient over one batch of ``batch`` samples
         for every device of ``models`` [D, P] (fp32 CUDA, unit element stride, any row pitch, read
         only) on the LeNet-family ``geom``, with the training set ``x`` [Nt, side, side] fp32 /
         ``labels`` [Nt] int32 all devices share, or [D, Nt, side, side] / [D, Nt] with one set per
@@ -646,8 +649,11 @@ class Engine:
         data; values outside [0, D) are the caller's error. ``first`` ([D] int64 CUDA, or None
         for 0): the first sample of every device's batch; a batch past the set's end wraps.
         ``skip`` ([D] int32 CUDA, or None): a flagged device's row and loss are not touched.
-        ``workspace``: ``lenet_grad_workspace(D, batch, geom)``. The library validates the rest
+        ``workspace``: ``lenet_grad_workspace(D, batch, geom)``. ``loss_kind``: the objective,
+        "xent" or "huber" as ``lenet_eval``'s ``loss`` (here ``loss`` is the output buffer);
+        ValueError for any other, before any device call. The library validates the rest
         (CFAError)."""
+        kind = _lib.lenet_loss_kind(loss_kind)
         geom = tuple(int(v) for v in geom)
         if len(geom) != 5:
             raise ValueError("geom must be (side, kernel, c1, c2, classes)")
@@ -684,9 +690,9 @@ class Engine:
         if pitch < P or gpitch < P:
             raise ValueError("models or grads rows overlap (pitch below P)")
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        _lib.call("cfa_lenet_grad_f32", x.data_ptr(), x_stride, labels.data_ptr(), label_stride, Nt, *geom,
+        _lib.call("cfa_lenet_grad_loss_f32", x.data_ptr(), x_stride, labels.data_ptr(), label_stride, Nt, *geom,
                   models.data_ptr(), pitch, D, ptr(src), ptr(first), batch, ptr(skip), grads.data_ptr(), gpitch,
-                  ptr(loss), workspace.data_ptr(), workspace.numel() * 4, self.stream_handle(stream))
+                  ptr(loss), workspace.data_ptr(), workspace.numel() * 4, kind, self.stream_handle(stream))
         return grads
 
     # -- local optimizer step of a TF2 population ---------------------------------------------

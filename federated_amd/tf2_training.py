@@ -5,9 +5,11 @@ updates: ``loss = reduce_mean(-sum(onehot * log(model(x))))``, ``tape.gradient``
 ``optimizer.apply_gradients``
 (``federated_learning_keras_consensus_FL_threads_MNIST_crossentropy_gradients_exchange.py:321-337``),
 and in the gradient-exchange variants it evaluates a neighbour's model on a batch of its own data
-and publishes that gradient (``:360-385``). ``LenetTraining`` holds what those steps need (the
+and publishes that gradient (``:360-385``). The drivers without ``crossentropy`` in their name
+train on ``keras.losses.Huber()`` between the label and the true class's probability instead
+(``federated_learning_keras_consensus_FL_MNIST.py:369-377``): ``loss="huber"``. ``LenetTraining`` holds what those steps need (the
 training set, the batch size, each device's position in its set, the gradient and loss buffers)
-and computes all D gradients in one ``cfa_lenet_grad_f32`` call, for the model family, geometry and
+and computes all D gradients in one ``cfa_lenet_grad_loss_f32`` call, for the model family, geometry and
 row layout of ``tf2_validation`` (``lenet_layer_shapes``). With ``PopulationOptimizer`` and
 ``LenetValidation`` one epoch of a population stays on the device::
 
@@ -25,6 +27,8 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
+from ._lib import lenet_loss_kind
+
 from .tf2_validation import LENET1, MAX_CLASSES, _stages, lenet_layer_shapes, lenet_size
 
 __all__ = ["LenetTraining", "lenet_size", "lenet_layer_shapes", "LENET1"]
@@ -36,7 +40,7 @@ class LenetTraining:
     @staticmethod
     def check(geom: Sequence[int], x_shape: Sequence[int], labels_shape: Sequence[int], batch: int,
               labels: Optional[np.ndarray] = None, src: Optional[np.ndarray] = None,
-              D: Optional[int] = None) -> dict:
+              D: Optional[int] = None, loss: str = "xent") -> dict:
         """The host half: validates geometry, shapes and the batch without touching a device and
         returns geom, P, Nt, batch and per_device (D, or 0 for the shared set). ``x_shape`` is
         [Nt, side, side] (the set all devices share) or [D, Nt, side, side], and ``labels_shape``
@@ -44,7 +48,9 @@ class LenetTraining:
         ``src`` (a host array, optional; needs ``D`` or a per-device set) to be one integer per
         device in [0, D). ValueError for a geometry without a model (p2 < 1) or with more than
         64 classes, mismatched shapes, ``batch`` below 1 or above Nt, a label or a ``src`` out of
-        range, and a ``D`` that disagrees with a per-device set."""
+        range, a ``D`` that disagrees with a per-device set and a ``loss`` other than "xent" or
+        "huber" (the plan is the same for both)."""
+        lenet_loss_kind(loss)
         side, k, c1, c2, classes, _ = _stages(geom)
         if classes > MAX_CLASSES:
             raise ValueError(f"more than {MAX_CLASSES} classes")
@@ -76,13 +82,18 @@ class LenetTraining:
         return {"geom": (side, k, c1, c2, classes), "P": lenet_size(geom), "Nt": Nt, "batch": batch,
                 "per_device": per_device}
 
-    def __init__(self, engine, geom: Sequence[int], x_train: torch.Tensor, labels: torch.Tensor, batch: int):
+    def __init__(self, engine, geom: Sequence[int], x_train: torch.Tensor, labels: torch.Tensor, batch: int,
+                 loss: str = "xent"):
         """``x_train`` [Nt, side, side] fp32 / ``labels`` [Nt] int32 (contiguous CUDA): the
         training set every device draws its batches from, or [D, Nt, side, side] / [D, Nt] with
         one set per device (the drivers' case). The labels are checked once, here, to lie in
-        [0, classes) (reads two values back: synchronises)."""
-        info = self.check(geom, x_train.shape, labels.shape, batch)
-        self.engine, self.geom, self.P = engine, info["geom"], info["P"]
+        [0, classes) (reads two values back: synchronises). ``loss``: the drivers' objective,
+        "xent" (``*_crossentropy*``) or "huber" (the others, e.g.
+        ``federated_learning_keras_consensus_FL_MNIST.py:369-377``: ``keras.losses.Huber()``
+        between the integer label itself and the softmax probability of the true class); it is
+        kept as ``loss_kind`` (``loss`` is the buffer of the batch losses)."""
+        info = self.check(geom, x_train.shape, labels.shape, batch, loss=loss)
+        self.engine, self.geom, self.P, self.loss_kind = engine, info["geom"], info["P"], loss
         self.x_train, self.labels = x_train, labels
         self.Nt, self.batch, self.per_device = info["Nt"], info["batch"], info["per_device"]
         if labels.dtype != torch.int32 or not labels.is_cuda:
@@ -131,7 +142,8 @@ class LenetTraining:
             src = torch.as_tensor(np.asarray(src, dtype=np.int32), device=self.engine.device)
         return self.engine.lenet_grad(self.geom, self.x_train, self.labels, models, self.batch,
                                       self.grads if out is None else out, self.workspace, self.loss, src,
-                                      self.cursor if first is None else first, skip, stream)
+                                      self.cursor if first is None else first, skip, stream,
+                                      loss_kind=self.loss_kind)
 
     def advance(self, skip: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``cursor[d] = (cursor[d] + batch) % Nt`` for every device not flagged in ``skip``, on

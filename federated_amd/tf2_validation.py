@@ -4,9 +4,11 @@ In the reference a device raises ``training_end`` from its own validation loss: 
 it runs its Keras model forward over the shared test set in batches, averages the batch losses
 and ends when the average falls under ``target_loss``
 (``federated_learning_keras_consensus_FL_threads_MNIST_crossentropy_gradients_exchange.py:430-455``;
-the model is ``create_q_model``, condition 0, ``:158-194``: LeNet-1, 2 202 parameters).
+the model is ``create_q_model``, condition 0, ``:158-194``: LeNet-1, 2 202 parameters; the drivers
+without ``crossentropy`` in their name validate on their Huber objective,
+``federated_learning_keras_consensus_FL_MNIST.py:481-483``: ``loss="huber"``).
 ``LenetValidation`` holds what that pass needs (the test set, the batching, the target and the
-cost buffers) and runs it for all D devices in one ``cfa_lenet_eval_f32`` call: every device's
+cost buffers) and runs it for all D devices in one ``cfa_lenet_eval_loss_f32`` call: every device's
 model stays in LDS for its batches, and the flags are written where the populations keep them.
 
 The model family is the "LeNet-1 family" ``geom = (side, kernel, c1, c2, classes)``::
@@ -33,6 +35,8 @@ from typing import Optional, Sequence
 
 import numpy as np
 import torch
+
+from ._lib import lenet_loss_kind
 
 __all__ = ["LenetValidation", "lenet_size", "lenet_layer_shapes", "LENET1"]
 
@@ -74,15 +78,16 @@ class LenetValidation:
     @staticmethod
     def check(geom: Sequence[int], x_shape: Sequence[int], labels_shape: Sequence[int], batch: int,
               batches: Optional[int] = None, target: Optional[float] = None, log_cap: int = 0,
-              labels: Optional[np.ndarray] = None) -> dict:
+              labels: Optional[np.ndarray] = None, loss: str = "xent") -> dict:
         """The host half: validates geometry, shapes and batching without touching a device and
         returns geom, P, Nt, batch, batches, per_device (D, or 0 for the shared set) and target.
         ``x_shape`` is [Nt, side, side] (the set all devices share) or [D, Nt, side, side], and
         ``labels_shape`` [Nt] or [D, Nt]. ``batches=None`` is the driver's ``int(Nt / batch)``.
         ``labels`` (a host array, optional) is checked to lie in [0, classes). ValueError for a
         geometry without a model (p2 < 1) or with more than 64 classes, mismatched shapes,
-        ``batch * batches > Nt``, a non-finite target, a negative ``log_cap`` and a label out of
-        range."""
+        ``batch * batches > Nt``, a non-finite target, a negative ``log_cap``, a label out of
+        range and a ``loss`` other than "xent" or "huber" (the plan is the same for both)."""
+        lenet_loss_kind(loss)
         side, k, c1, c2, classes, _ = _stages(geom)
         if classes > MAX_CLASSES:
             raise ValueError(f"more than {MAX_CLASSES} classes")
@@ -112,15 +117,19 @@ class LenetValidation:
                 "target": None if target is None else float(target)}
 
     def __init__(self, engine, geom: Sequence[int], x_test: torch.Tensor, labels: torch.Tensor, batch: int,
-                 batches: Optional[int] = None, target: Optional[float] = None, log_cap: int = 0):
+                 batches: Optional[int] = None, target: Optional[float] = None, log_cap: int = 0,
+                 loss: str = "xent"):
         """``x_test`` [Nt, side, side] fp32 / ``labels`` [Nt] int32 (contiguous CUDA): the test
         set every device validates on, or [D, Nt, side, side] / [D, Nt] with one set per device.
         ``target``: the driver's ``target_loss``, needed to raise flags. ``log_cap`` > 0 keeps a
         [log_cap, D] log of the cost on the device: call e goes to row min(e, log_cap - 1). The
         labels are checked once, here, to lie in [0, classes) (reads two values back:
-        synchronises)."""
-        info = self.check(geom, x_test.shape, labels.shape, batch, batches, target, log_cap)
-        self.engine, self.geom, self.P = engine, info["geom"], info["P"]
+        synchronises). ``loss``: the drivers' objective, "xent" (``*_crossentropy*``:
+        ``-log softmax(z)[label]``) or "huber" (the others, e.g.
+        ``federated_learning_keras_consensus_FL_MNIST.py:481-483``: ``keras.losses.Huber()``
+        between the integer label itself and the softmax probability of the true class)."""
+        info = self.check(geom, x_test.shape, labels.shape, batch, batches, target, log_cap, loss=loss)
+        self.engine, self.geom, self.P, self.loss_kind = engine, info["geom"], info["P"], loss
         self.x_test, self.labels = x_test, labels
         self.Nt, self.batch, self.batches, self.target = info["Nt"], info["batch"], info["batches"], info["target"]
         self.per_device, self.log_cap = info["per_device"], int(log_cap)
@@ -170,4 +179,5 @@ class LenetValidation:
         logged = self.val_log is not None
         return self.engine.lenet_eval(self.geom, self.x_test, self.labels, models, self.batch, self.batches,
                                       self.val_cost, self.workspace, skip, self.target or 0.0, ended,
-                                      self.val_log, self.epoch_counter if logged else None, stream)
+                                      self.val_log, self.epoch_counter if logged else None, stream,
+                                      loss=self.loss_kind)

@@ -166,6 +166,12 @@ enum {
   CFA_OPTIM_ADAM = 2      /* Keras Adam without amsgrad, tf.clip_by_norm per layer first   Adam(learning_rate, clipnorm) */
 };
 
+/* The objective of the TF2 LeNet-1 kernels (cfa_lenet_eval_loss_f32, cfa_lenet_grad_loss_f32). */
+enum {
+  CFA_LENET_LOSS_XENT = 0, /* -log softmax(z)[label]                 ..._MNIST_crossentropy_gradients_exchange.py:321-337 */
+  CFA_LENET_LOSS_HUBER = 1 /* Huber(label, softmax(z)[label])        federated_learning_keras_consensus_FL_MNIST.py:369-377 */
+};
+
 CFA_API int cfa_version(void);
 CFA_API const char* cfa_last_error(void);
 
@@ -694,6 +700,27 @@ CFA_API int cfa_lenet_eval_f32(const float* x, size_t x_dev_stride, const int32_
                                double* cost, double* cost_log, int log_cap, unsigned long long* epoch,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same pass on the objective `loss` (CFA_LENET_LOSS_*); cfa_lenet_eval_f32 is this call with
+ * CFA_LENET_LOSS_XENT, bit for bit. CFA_LENET_LOSS_HUBER is the objective of the drivers that
+ * train LeNet-1 with keras.losses.Huber() (federated_learning_keras_consensus_FL_MNIST.py:125,
+ * validation :481-483; ..._FL_threads_MNIST_gradients_exchange.py:442-447; the PS drivers): the
+ * Huber loss, delta = 1, between the integer label ITSELF, cast to float, and the softmax
+ * probability of the true class. Per sample with label l:
+ *   p = exp(z_l - max) / sum_c exp(z_c - max);  e = p - (float)l          (fp32, classes in order)
+ *   h = 0.5 e^2 where |e| <= 1, else |e| - 0.5
+ * and loss_b is the mean of h over the batch, summed and divided as above. With 0 < p < 1 the
+ * label picks the branch (0: quadratic in p; 1: quadratic in 1 - p; 2 and above: linear). Where p
+ * rounds to exactly 0 or 1, e reaches a branch's edge; <= keeps the quadratic branch, as Keras
+ * does, and both branches have the same value and slope there. A label outside [0, classes) gives
+ * a NaN cost. Every other argument, the workspace, the determinism and the refusals are those of
+ * cfa_lenet_eval_f32; CFA_E_INVALID also for an unknown loss (checked first, before any buffer). */
+CFA_API int cfa_lenet_eval_loss_f32(const float* x, size_t x_dev_stride, const int32_t* labels,
+                                    size_t label_dev_stride, int Nt, int side, int kernel, int c1, int c2,
+                                    int classes, const float* models, size_t pitch, int D, int batch, int batches,
+                                    const int32_t* skip, double target, int32_t* ended,
+                                    double* cost, double* cost_log, int log_cap, unsigned long long* epoch,
+                                    void* workspace, size_t workspace_bytes, int loss, void* stream);
+
 /* (TF2 drivers) A minibatch's loss and gradient for every device of a LeNet-1 population, the
  * model family, row layout and geometry of the block above: the local update's
  *   loss = reduce_mean(-sum(onehot * log(model(x)))); grads = tape.gradient(loss, weights)
@@ -735,6 +762,25 @@ CFA_API int cfa_lenet_grad_f32(const float* x, size_t x_dev_stride, const int32_
                                const long long* first, int batch, const int32_t* skip,
                                float* grads, size_t gpitch, float* loss,
                                void* workspace, size_t workspace_bytes, void* stream);
+
+/* The same gradient on the objective `loss_kind` (CFA_LENET_LOSS_*); cfa_lenet_grad_f32 is this
+ * call with CFA_LENET_LOSS_XENT, bit for bit. CFA_LENET_LOSS_HUBER: the local update of the Huber
+ * drivers,
+ *   class_v = reduce_sum(classes * masks, axis=1); loss = Huber()(label_sample, class_v)
+ * (federated_learning_keras_consensus_FL_MNIST.py:369-377;
+ * ..._FL_threads_MNIST_gradients_exchange.py:327-335, and at a neighbour's model :364-380), with
+ * p, e and h of cfa_lenet_eval_loss_f32 and, at the logits,
+ *   dz[c] = (g p) ((c == l) - exp(z_c - max) / sum),  g = e where |e| <= 1, else sign(e);
+ * everything behind dz, the 1 / batch factor, the groups of 4 samples and the loss's bit-for-bit
+ * agreement with cfa_lenet_eval_loss_f32 on the same samples are as above. A label outside
+ * [0, classes) makes that device's loss and whole row NaN. CFA_E_INVALID also for an unknown
+ * loss_kind (checked first, before any buffer). */
+CFA_API int cfa_lenet_grad_loss_f32(const float* x, size_t x_dev_stride, const int32_t* labels,
+                                    size_t label_dev_stride, int Nt, int side, int kernel, int c1, int c2,
+                                    int classes, const float* models, size_t pitch, int D, const int32_t* src,
+                                    const long long* first, int batch, const int32_t* skip,
+                                    float* grads, size_t gpitch, float* loss,
+                                    void* workspace, size_t workspace_bytes, int loss_kind, void* stream);
 
 /* (a1-a6 batched) Population round: one launch mixes D devices.
  * For device d, CSR entries e in [csr_ptr[d], csr_ptr[d+1]) list its sources in order; the

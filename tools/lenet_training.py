@@ -10,12 +10,14 @@ batches of 100 out of a per-device training set) timed in three forms on the sam
   torch-ROCm forward passes (conv2d, avg_pool2d, matmul, log_softmax) with autograd.grad on the same
   batch, the six gradients of each device copied into its row of a [D, P] stack.
 
+``--loss huber`` times all three on the Huber drivers' objective instead of the cross-entropy one.
+
 Every form runs windows of back-to-back calls between two device events, ending in a
 synchronise; the forms alternate window by window after ``--warmup`` untimed windows each.
 Reported: the median window over ``--reps`` per call in milliseconds with its extremes, torch's
 median over the device's, and how far the two forms' gradients are apart normwise (the largest
 over the six tensors and the devices). Prints one JSON line and appends it to ``--out``.
-Usage: python tools/lenet_training.py [--out profiles/lenet_training.jsonl]"""
+Usage: python tools/lenet_training.py [--loss xent|huber] [--out profiles/lenet_training.jsonl]"""
 import argparse
 import json
 import os
@@ -50,6 +52,7 @@ def main():
     ap.add_argument("--torch-calls", type=int, default=2, help="torch passes per timed window")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--loss", choices=("xent", "huber"), default="xent", help="the drivers' objective, all forms")
     ap.add_argument("--out", default=os.path.join("profiles", "lenet_training.jsonl"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -65,7 +68,7 @@ def main():
     W0 = torch.from_numpy((0.1 * rng.standard_normal((D, P))).astype(np.float32)).cuda()
     W = W0.clone()
     shapes = lenet_layer_shapes(geom)
-    tr = LenetTraining(eng, geom, x, labels, BATCH).allocate(D)
+    tr = LenetTraining(eng, geom, x, labels, BATCH, loss=a.loss).allocate(D)
     opt = PopulationOptimizer(eng, D, shapes, "adam", 1e-3, clipnorm=1.0)
     zero = torch.zeros(D, dtype=torch.int64, device="cuda")
 
@@ -80,7 +83,11 @@ def main():
             h = F.avg_pool2d(F.relu(F.conv2d(x4[d, :BATCH], K1.permute(3, 2, 0, 1), b1)), 2)
             h = F.avg_pool2d(F.relu(F.conv2d(h, K2.permute(3, 2, 0, 1), b2)), 2)
             h = h.permute(0, 2, 3, 1).reshape(BATCH, -1)
-            loss = F.nll_loss(F.log_softmax(h @ Wd + bd, dim=1), lab64[d, :BATCH])
+            if a.loss == "huber":  # Huber(label, softmax(z)[label]), delta = 1
+                p = torch.softmax(h @ Wd + bd, dim=1).gather(1, lab64[d, :BATCH, None])[:, 0]
+                loss = F.huber_loss(p, lab64[d, :BATCH].float(), delta=1.0)
+            else:
+                loss = F.nll_loss(F.log_softmax(h @ Wd + bd, dim=1), lab64[d, :BATCH])
             for i, g in enumerate(torch.autograd.grad(loss, ts)):
                 tgrads[d, offs[i]:offs[i + 1]] = g.reshape(-1)
 
@@ -117,7 +124,8 @@ def main():
             times[name].append(window(fn, n, per))
     med = {n: statistics.median(t) for n, t in times.items()}
     macs = macs_per_image(geom) * BATCH * D
-    rec = {"tool": "lenet_training", "device": torch.cuda.get_device_name(0), "devices": D, "train_images": NT,
+    rec = {"tool": "lenet_training", "device": torch.cuda.get_device_name(0), "loss": a.loss, "devices": D,
+           "train_images": NT,
            "batch": BATCH, "epoch_batches": a.batches, "geom": list(geom), "params": P, "reps": a.reps,
            "calls_per_window": {"gradients": a.calls, "epoch": a.epochs, "torch": a.torch_calls},
            "gradients_ms": round(med["gradients"], 4), "epoch_ms_per_batch": round(med["epoch"], 4),

@@ -13,8 +13,9 @@ Every form runs windows of back-to-back passes (``--passes`` / ``--torch-passes`
 device events and ending in a synchronise; the forms alternate window by window after
 ``--warmup`` untimed windows each. Reported: the median window over ``--reps``, per pass, in
 milliseconds, torch's median over the device's, how far the two forms' costs are apart, and the
-device form's multiply-add rate from the shapes. Prints one JSON line and appends it to ``--out``.
-Usage: python tools/lenet_validation.py [--out profiles/lenet_validation.jsonl]"""
+device form's multiply-add rate from the shapes. ``--loss huber`` times both forms on the Huber
+drivers' objective instead of the cross-entropy one. Prints one JSON line and appends it to ``--out``.
+Usage: python tools/lenet_validation.py [--loss xent|huber] [--out profiles/lenet_validation.jsonl]"""
 import argparse
 import json
 import os
@@ -45,6 +46,7 @@ def main():
     ap.add_argument("--torch-passes", type=int, default=1, help="torch passes per timed window")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--loss", choices=("xent", "huber"), default="xent", help="the drivers' objective, both forms")
     ap.add_argument("--out", default=os.path.join("profiles", "lenet_validation.jsonl"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -58,7 +60,7 @@ def main():
     x = torch.from_numpy(rng.random((NT, geom[0], geom[0])).astype(np.float32)).cuda()
     labels = torch.from_numpy(rng.integers(0, geom[4], NT).astype(np.int32)).cuda()
     W = torch.from_numpy((0.1 * rng.standard_normal((D, P))).astype(np.float32)).cuda()
-    val = LenetValidation(eng, geom, x, labels, BATCH).allocate(D)
+    val = LenetValidation(eng, geom, x, labels, BATCH, loss=a.loss).allocate(D)
 
     # the torch form's tensors, cut out ahead of the timed windows
     shapes = lenet_layer_shapes(geom)
@@ -82,8 +84,12 @@ def main():
                 h = F.avg_pool2d(F.relu(F.conv2d(x4[sl], K1, b1)), 2)
                 h = F.avg_pool2d(F.relu(F.conv2d(h, K2, b2)), 2)
                 h = h.permute(0, 2, 3, 1).reshape(BATCH, -1)
-                lp = F.log_softmax(h @ Wd + bd, dim=1)
-                acc += F.nll_loss(lp, lab64[sl]).double()
+                if a.loss == "huber":  # Huber(label, softmax(z)[label]), delta = 1
+                    p = torch.softmax(h @ Wd + bd, dim=1).gather(1, lab64[sl, None])[:, 0]
+                    acc += F.huber_loss(p, lab64[sl].float(), delta=1.0).double()
+                else:
+                    lp = F.log_softmax(h @ Wd + bd, dim=1)
+                    acc += F.nll_loss(lp, lab64[sl]).double()
             tcost[d] = acc / batches
 
     forms = {"device": (device_form, a.passes), "torch": (torch_form, a.torch_passes)}
@@ -107,7 +113,8 @@ def main():
             times[name].append(window(fn, n))
     med = {n: statistics.median(t) for n, t in times.items()}
     macs = macs_per_image(geom) * BATCH * batches * D
-    rec = {"tool": "lenet_validation", "device": torch.cuda.get_device_name(0), "devices": D, "test_images": NT,
+    rec = {"tool": "lenet_validation", "device": torch.cuda.get_device_name(0), "loss": a.loss, "devices": D,
+           "test_images": NT,
            "batch": BATCH, "batches": batches, "geom": list(geom), "params": P, "reps": a.reps,
            "passes_per_window": {"device": a.passes, "torch": a.torch_passes},
            "device_ms": round(med["device"], 4), "torch_ms": round(med["torch"], 3),
