@@ -39,6 +39,7 @@ extern "C" int cfa_device_prepare(int device) {
   int rc = grad_prepare_device();
   if (rc == CFA_OK) rc = local_sgd_prepare_device();
   if (rc == CFA_OK) rc = lenet_prepare_device();
+  if (rc == CFA_OK) rc = ring_prepare_device();
   if (device != prev) CFA_HIP_CHECK(hipSetDevice(prev));
   return rc;
 }

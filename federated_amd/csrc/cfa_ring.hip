@@ -120,8 +120,16 @@ __global__ __launch_bounds__(kBlock) void ring_round_kernel(RingArgs ra, long lo
 // W = HL+HR+1: device m of the segment folds stream rows m .. m+W-1 (its local row is m+HL) while
 // the loads of rows m+W .. m+W-1+PF are in flight. The device loop is unrolled W + PF times, so
 // stream row q always sits in slot q mod (W + PF) and every register index is static. A segment
-// re-reads HL+HR halo rows: a call reads count + segments * (HL+HR) rows. The fold is the window
-// pass's (ring_fold), on the slots the window's rows sit in, per vector.
+// re-reads HL+HR halo rows: a call of S segments reads count + S*K - (full ring ? K : 0) rows,
+// K = HL+HR. The fold is the window pass's (ring_fold), on the slots the window's rows sit in, per
+// vector.
+//
+// Seam rows once (SEAM, launched where slide_takes_seam allows): the stream of a full ring in one segment ends
+// with the K rows it began with. While priming, a lane keeps a second copy of those rows' U
+// vectors, the first K - slide_seam_lds_rows(K) in registers and the rest in LDS; the walk's last
+// K "loads" take the copies and issue no global load. A lane reads back only what it wrote itself
+// (vector (row * U + v) * kBlock + lane of the workgroup's LDS), so there is no barrier. Fold,
+// operand order and stores are the plain walk's; PF is 1 and the stores nontemporal.
 // ------------------------------------------------------------------------------------------
 struct SlideArgs {
   const float* in;
@@ -132,10 +140,19 @@ struct SlideArgs {
   int rows, first, count, seg;     // seg: devices per segment
 };
 
-template <int HL, int HR, int PF, int U, bool SC1>
-__global__ __launch_bounds__(kBlock) void ring_slide_kernel(SlideArgs sa, long long nvec) {
+__device__ __forceinline__ f4* slide_seam_lds() {
+  extern __shared__ __attribute__((aligned(16))) f4 seam_lds[];
+  return seam_lds;
+}
+
+// SEAM is held to the occupancy of the plain kernel's tuned shapes (slide_seam_waves per SIMD).
+template <int HL, int HR, int PF, int U, bool SC1, bool SEAM = false>
+__global__ __launch_bounds__(kBlock, SEAM ? slide_seam_waves(U) : 1) void ring_slide_kernel(SlideArgs sa,
+                                                                                            long long nvec) {
   constexpr int W = HL + HR + 1;
   constexpr int RS = W + PF;
+  constexpr int K = HL + HR;                               // seam rows of a full ring
+  constexpr int KV = SEAM ? K - slide_seam_lds_rows(K) : 0;  // of them, kept in registers
   constexpr long long kTile = (long long)kBlock * U;
   const int n0 = (int)blockIdx.y * sa.seg;  // first device of the segment, relative to sa.first
   const int len = min(sa.seg, sa.count - n0);
@@ -174,13 +191,46 @@ __global__ __launch_bounds__(kBlock) void ring_slide_kernel(SlideArgs sa, long l
 #pragma unroll
     for (int q = 0; q < RS - 1; ++q)
       if (q < total) load_row(r[q]);
+    // SEAM: the lane's second copy of stream rows 0 .. K-1 (all primed above: total > RS - 1 > K on
+    // a full ring), the first KV in registers and the rest in the lane's own LDS vectors.
+    [[maybe_unused]] f4 keep[KV > 0 ? KV : 1][U];
+    if constexpr (SEAM) {
+#pragma unroll
+      for (int q = 0; q < K; ++q)
+#pragma unroll
+        for (int v = 0; v < U; ++v) {
+          if (q < KV) keep[q][v] = r[q][v];
+          else slide_seam_lds()[((q - KV) * U + v) * kBlock + threadIdx.x] = r[q][v];
+        }
+    }
     for (int n = 0; n < len; n += RS) {
 #pragma unroll
       for (int u = 0; u < RS; ++u) {
         const int m = n + u;
         if (m < len) {
           // stream row m+W-1+PF: into the slot row m-1 has left
-          if (m + RS - 1 < total) load_row(r[(u + RS - 1) % RS]);
+          if constexpr (SEAM) {
+            // rows len .. len+K-1 of a full ring's stream are its rows 0 .. K-1 again
+            if (m + RS - 1 >= len) {
+              const int j = m + RS - 1 - len;  // retained row j instead of its loads
+              f4(&slot)[U] = r[(u + RS - 1) % RS];
+              if (j >= K) {  // past the stream's end
+              } else if (j >= KV) {
+#pragma unroll
+                for (int v = 0; v < U; ++v) slot[v] = slide_seam_lds()[((j - KV) * U + v) * kBlock + threadIdx.x];
+              } else {
+#pragma unroll
+                for (int k = 0; k < KV; ++k)  // uniform branches: every register index static
+                  if (j == k)
+#pragma unroll
+                    for (int v = 0; v < U; ++v) slot[v] = keep[k][v];
+              }
+            } else {
+              load_row(r[(u + RS - 1) % RS]);
+            }
+          } else {
+            if (m + RS - 1 < total) load_row(r[(u + RS - 1) % RS]);
+          }
           const float a = sa.alphas[n0 + m];
           f4 acc[U];
 #pragma unroll
@@ -285,7 +335,9 @@ void launch_ring_round(const RingArgs& ra, long long nvec, hipStream_t st) {
 // one process can compare shapes on the same buffers (tools/probe/ring_slide.py); results are
 // identical for every shape. SlideTune and its default are in cfa_slide_shape.h; here u = 0 stands
 // for the tuned width, stepped down where a short row would leave workgroups without a tile
-// (slide_pick_u), and CFA_SLIDE_U = 1, 2 or 4 for exactly that width.
+// (slide_pick_u), and CFA_SLIDE_U = 1, 2 or 4 for exactly that width. CFA_SLIDE_SEAM = 0 keeps a
+// full ring on the plain kernel, 1 sends it to the seam kernel where slide_takes_seam allows
+// (nontemporal stores only; the seam kernel's PF is 1 whatever CFA_SLIDE_PF says).
 static_assert(kSlideBlock == kBlock, "cfa_slide_shape.h counts tiles of kBlock lanes");
 static SlideTune slide_tune() {
   const SlideTune d = kSlideDefault;
@@ -309,9 +361,41 @@ void launch_slide_u(const SlideArgs& c, long long m, dim3 grid, const SlideTune&
     default: launch_slide_shape<HL, HR, 2, U>(c, m, grid, t.sc1, st); break;
   }
 }
+// The seam kernel of a full ring in one segment; false (nothing launched) where the window retains
+// nothing or the device refuses the kernel its LDS. Above 64 KB the kernel's dynamic-LDS limit is
+// raised first, once per device (as cfa_grad.hip's kernels).
+template <int HL, int HR, int U>
+bool slide_seam_lds_ready() {
+  constexpr int bytes = slide_seam_lds_bytes(HL + HR, U);
+  if constexpr (bytes > 65536) {
+    static unsigned long long raised = 0;  // bit per device
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
+    if (__atomic_load_n(&raised, __ATOMIC_RELAXED) >> dev & 1) return true;
+    if (bytes > device_lds_max() ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&ring_slide_kernel<HL, HR, 1, U, false, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      return false;
+    }
+    __atomic_fetch_or(&raised, 1ULL << dev, __ATOMIC_RELAXED);
+  }
+  return true;
+}
+template <int HL, int HR, int U>
+bool launch_slide_seam(const SlideArgs& c, long long m, dim3 grid, hipStream_t st) {
+  if constexpr (HL + HR >= 1) {
+    if (!slide_seam_lds_ready<HL, HR, U>()) return false;
+    ring_slide_kernel<HL, HR, 1, U, false, true><<<grid, kBlock, slide_seam_lds_bytes(HL + HR, U), st>>>(c, m);
+    return true;
+  } else {
+    return false;
+  }
+}
 template <int HL, int HR>
 void launch_ring_slide(const SlideArgs& sa, long long nvec, hipStream_t st) {
   const SlideTune t = slide_tune();
+  const bool seam_wanted = env_int("CFA_SLIDE_SEAM", kSlideSeamDefault) != 0 && !t.sc1;
   int segments = t.segments < sa.count ? t.segments : sa.count;
   if (segments > 65535) segments = 65535;
   SlideArgs c = sa;
@@ -322,6 +406,9 @@ void launch_ring_slide(const SlideArgs& sa, long long nvec, hipStream_t st) {
     const int u = t.u ? t.u : slide_pick_u(m, kSlideDefault.u, device_cus(), t.wg_per_cu);
     // the launch's workgroups over all segments: about wg_per_cu per CU in all
     const dim3 grid(shared_grid_x(slide_tiles(m, u), t.wg_per_cu, gy), gy);
+    if (seam_wanted && slide_takes_seam(sa.rows, sa.count, (int)gy, HL, HR, u) &&
+        (u == 4 ? launch_slide_seam<HL, HR, 4>(c, m, grid, st) : launch_slide_seam<HL, HR, 2>(c, m, grid, st)))
+      return;
     switch (u) {
       case 4: launch_slide_u<HL, HR, 4>(c, m, grid, t, st); break;
       case 2: launch_slide_u<HL, HR, 2>(c, m, grid, t, st); break;
@@ -337,9 +424,23 @@ void launch_ring_slide(const SlideArgs& sa, long long nvec, hipStream_t st) {
 void (*const kWindowLaunch[5][5])(const WindowArgs&, long long, hipStream_t) = CFA_HLHR_TABLE(launch_window);
 void (*const kRingLaunch[5][5])(const RingArgs&, long long, hipStream_t) = CFA_HLHR_TABLE(launch_ring_round);
 void (*const kSlideLaunch[5][5])(const SlideArgs&, long long, hipStream_t) = CFA_HLHR_TABLE(launch_ring_slide);
+template <int HL, int HR>
+void slide_seam_prepare() {
+  if constexpr (HL + HR >= 1) (void)(slide_seam_lds_ready<HL, HR, 4>() && slide_seam_lds_ready<HL, HR, 2>());
+}
+void (*const kSlideSeamPrepare[5][5])() = CFA_HLHR_TABLE(slide_seam_prepare);
 #undef CFA_HLHR_TABLE
 #undef CFA_HLHR_ROW
 }  // namespace
+
+// Current device: raise the seam kernels' dynamic-LDS limit now (cfa_device_prepare), so later
+// launches (e.g. under hipGraph capture) need no attribute call. Refused: those windows' full
+// rings stay on the plain kernel.
+int ring_prepare_device() {
+  for (int hl = 0; hl <= 4; ++hl)
+    for (int hr = 0; hr <= 4; ++hr) kSlideSeamPrepare[hl][hr]();
+  return CFA_OK;
+}
 
 extern "C" int cfa_mix_window_f32(float* const* out, const float* const* rows, const float* alphas,
                                   int nb, int hl, int hr, size_t P, void* stream) {

@@ -28,3 +28,21 @@ inline int slide_pick_u(long long nvec, int want, int cus, int wg_per_cu) {
   while (u > 1 && slide_tiles(nvec, u) < (long long)cus * wg_per_cu) u >>= 1;
   return u;
 }
+
+// Seam rows once: a full ring walked in one segment ends with the hl + hr rows it began with, and
+// the seam kernel keeps a lane's copy of them (registers and LDS) instead of loading them again.
+// Of the k = hl + hr retained rows at most kSlideSeamLdsRows sit in LDS, the others in registers:
+// 5 rows of a u = 4 tile are 80 KB, so two workgroups share a CU's 160 KB (four at u = 2), the
+// resident tile width of the plain kernel's tuned shapes.
+constexpr int kSlideSeamDefault = 1;  // tools/probe/ring_slide.py sweep, profiles/r13_slide_seam_sweep.jsonl
+constexpr int kSlideSeamLdsRows = 5;
+constexpr int slide_seam_lds_rows(int k) { return k < kSlideSeamLdsRows ? k : kSlideSeamLdsRows; }
+constexpr int slide_seam_lds_bytes(int k, int u) { return slide_seam_lds_rows(k) * u * kSlideBlock * 16; }
+constexpr int slide_seam_waves(int u) { return u >= 4 ? 2 : 4;  }  // waves per SIMD the kernel is held to
+
+// Whether a call of `count` devices of a ring of `rows`, in `segments` segments at u float4 per
+// lane (after slide_pick_u's step-down), takes the seam kernel: a full ring in one segment with a
+// window to retain, at a tile width that has a seam instantiation (2, 4).
+inline bool slide_takes_seam(int rows, int count, int segments, int hl, int hr, int u) {
+  return count == rows && segments == 1 && hl + hr >= 1 && (u == 2 || u == 4);
+}

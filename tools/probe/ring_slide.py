@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """The sliding ring round (cfa_mix_ring_slide_f32) on the bench's population (128 devices x 25M
 fp32, K = 8 by default). The kernel reads its launch shape from the environment at every launch
-(CFA_SLIDE_SEGMENTS, CFA_SLIDE_PF, CFA_SLIDE_WG_PER_CU, CFA_SLIDE_SC1, CFA_SLIDE_U; results
-identical), so one process compares shapes on the same stacks. One JSON line per record.
+(CFA_SLIDE_SEGMENTS, CFA_SLIDE_PF, CFA_SLIDE_WG_PER_CU, CFA_SLIDE_SC1, CFA_SLIDE_U, CFA_SLIDE_SEAM;
+results identical), so one process compares shapes on the same stacks. One JSON line per record.
 
   ring_slide.py sweep            every shape, interleaved over passes: median us per round
   ring_slide.py ab [reps]        the slide round (shape from the environment) alternated with
@@ -10,7 +10,8 @@ identical), so one process compares shapes on the same stacks. One JSON line per
   ring_slide.py once [launches]  only slide launches (for rocprofv3 --pmc runs, one counter per run)
 
 Environment: RS_DEVICES, RS_P, RS_H (window half-width), RS_SEGMENTS / RS_PF / RS_WG / RS_SC1 /
-RS_U (comma lists of the sweep; RS_U: float4 per lane and row, 1, 2 or 4), RS_PASSES."""
+RS_U / RS_SEAM (comma lists of the sweep; RS_U: float4 per lane and row, 1, 2 or 4; RS_SEAM: 1 the
+seam kernel where the launch rule allows it, 0 the plain kernel), RS_PASSES."""
 import itertools
 import json
 import os
@@ -34,10 +35,11 @@ def ints(name, default):
     return [int(x) for x in os.environ.get(name, default).split(",")]
 
 
-def moved_bytes(segments):
+def moved_bytes(segments, seam=0, u=4):
     s = min(segments, D)
     seg = -(-D // s)
-    return (2 * D + -(-D // seg) * K) * P * 4
+    halo = 0 if seam and s == 1 and K and u in (2, 4) else -(-D // seg) * K  # slide_takes_seam
+    return (2 * D + halo) * P * 4
 
 
 def main():
@@ -51,7 +53,7 @@ def main():
     def slide(shape=None):
         if shape is not None:
             for key, v in zip(("CFA_SLIDE_SEGMENTS", "CFA_SLIDE_PF", "CFA_SLIDE_WG_PER_CU", "CFA_SLIDE_SC1",
-                               "CFA_SLIDE_U"), shape):
+                               "CFA_SLIDE_U", "CFA_SLIDE_SEAM"), shape):
                 os.environ[key] = str(v)
         eng.ring_slide(out, models, alphas, 0, D, H, H)
 
@@ -81,15 +83,16 @@ def main():
                       flush=True)
     else:
         shapes = list(itertools.product(ints("RS_SEGMENTS", "1"), ints("RS_PF", "1,2"),
-                                        ints("RS_WG", "1,2,4"), ints("RS_SC1", "0"), ints("RS_U", "1,2,4")))
+                                        ints("RS_WG", "1,2,4"), ints("RS_SC1", "0"), ints("RS_U", "1,2,4"),
+                                        ints("RS_SEAM", "0,1")))
         times = {s: [] for s in shapes}
         for _ in range(int(os.environ.get("RS_PASSES", "3"))):
             for s in shapes:
                 times[s].append(timed(lambda: slide(s)))
         for s in sorted(shapes, key=lambda s: statistics.median(times[s])):
             us = statistics.median(times[s])
-            mb = moved_bytes(s[0])
-            print(json.dumps(dict(base, segments=s[0], pf=s[1], wg_per_cu=s[2], sc1=s[3], u=s[4],
+            mb = moved_bytes(s[0], s[5] and not s[3], s[4])
+            print(json.dumps(dict(base, segments=s[0], pf=s[1], wg_per_cu=s[2], sc1=s[3], u=s[4], seam=s[5],
                                   us_per_round=round(us, 2), spread_us=round(max(times[s]) - min(times[s]), 2),
                                   moved_bytes=mb, moved_frac_of_peak=round(mb / (us * 1e-6) / PEAK, 4))), flush=True)
 
