@@ -48,6 +48,16 @@ def lenet_loss_kind(loss) -> int:
         raise ValueError(f"loss must be one of {sorted(LENET_LOSSES)}, got {loss!r}")
     return LENET_LOSSES[loss]
 
+LENET_POOLS = ("avg", "max")  # the pooling rule of the two-stage conv family: cfa_lenet_* / cfa_lenet_max_*
+
+
+def lenet_pool(pool) -> str:
+    """The infix of the entry points of a pooling rule ("avg": "", "max": "max_"); ValueError for
+    anything else."""
+    if not isinstance(pool, str) or pool not in LENET_POOLS:
+        raise ValueError(f"pool must be one of {list(LENET_POOLS)}, got {pool!r}")
+    return "" if pool == "avg" else "max_"
+
 COMPRESS_NONE = 0
 COMPRESS_SPARSE = 1
 COMPRESS_SPARSE_DPCM = 2
@@ -171,6 +181,16 @@ SIGNATURES = {
                                          _c_int, _c_int, _c_void_p, _c_size_t, _c_int, _c_void_p, _c_void_p, _c_int,
                                          _c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_int,
                                          _c_void_p]),
+    "cfa_lenet_max_eval_workspace_bytes": (_c_size_t, [_c_int, _c_int]),
+    "cfa_lenet_max_eval_loss_f32": (_c_int, [_c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_int, _c_int, _c_int,
+                                             _c_int, _c_int, _c_int, _c_void_p, _c_size_t, _c_int, _c_int, _c_int,
+                                             _c_void_p, ctypes.c_double, _c_void_p, _c_void_p, _c_void_p, _c_int,
+                                             _c_void_p, _c_void_p, _c_size_t, _c_int, _c_void_p]),
+    "cfa_lenet_max_grad_workspace_bytes": (_c_size_t, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int]),
+    "cfa_lenet_max_grad_loss_f32": (_c_int, [_c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_int, _c_int, _c_int,
+                                             _c_int, _c_int, _c_int, _c_void_p, _c_size_t, _c_int, _c_void_p,
+                                             _c_void_p, _c_int, _c_void_p, _c_void_p, _c_size_t, _c_void_p,
+                                             _c_void_p, _c_size_t, _c_int, _c_void_p]),
     "cfa_optim_tile": (_c_int, []),
     "cfa_optim_workspace_bytes": (_c_size_t, [_c_int, _c_size_t, _c_int]),
     "cfa_optim_step_f32": (_c_int, [_c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t,

@@ -20,17 +20,6 @@ namespace {
 constexpr int kLenetBlock = 256;  // 4 waves; several workgroups share a CU and overlap their barriers
 constexpr int kLenetChunk = 4;    // samples per pass through the phases
 
-struct LenetArgs {
-  const float* x;         // [Nt][side][side], or [D][Nt][side][side] with x_stride
-  const int32_t* labels;  // [Nt], or [D][Nt] with label_stride
-  long long x_stride, label_stride;
-  const float* models;    // [D][pitch]
-  long long pitch;
-  int batch, batches;
-  const int32_t* skip;    // [D] or null
-  float* ws;              // [D][batches] batch losses
-};
-
 // LDS floats of the evaluation kernel: the model, a chunk's activations, a batch's losses.
 inline long long lenet_eval_lds(const LenetGeom& g, int batch) {
   return g.P + (long long)kLenetChunk * lenet_sample_floats(g) + batch;
@@ -78,45 +67,6 @@ __global__ __launch_bounds__(kLenetBlock) void lenet_eval_kernel(LenetArgs a, Le
   }
 }
 
-struct LenetFinish {
-  const float* ws;
-  int D, batches;
-  const int32_t* skip;
-  double target;
-  int32_t* ended;  // or null
-  double* cost;
-  double* cost_log;  // or null
-  int log_cap;
-  unsigned long long* epoch;  // or null, with cost_log
-};
-
-// One workgroup. Thread d % T owns device d: its cost, its flag (read before it is written, so
-// skip and ended may be one array) and its log entry.
-__global__ __launch_bounds__(kLenetBlock) void lenet_finish_kernel(LenetFinish f) {
-  unsigned long long row = 0;
-  if (f.cost_log) {
-    const unsigned long long e = *f.epoch, last = (unsigned long long)(f.log_cap - 1);
-    row = e < last ? e : last;
-  }
-  for (int d = threadIdx.x; d < f.D; d += blockDim.x) {
-    double c;
-    if (f.skip && f.skip[d]) {
-      c = f.cost[d];
-    } else {
-      double acc = 0.0;
-      for (int b = 0; b < f.batches; ++b) acc += (double)f.ws[(long long)d * f.batches + b];
-      c = acc / (double)f.batches;
-      f.cost[d] = c;
-      if (f.ended) f.ended[d] = f.ended[d] | (c < f.target ? 1 : 0);
-    }
-    if (f.cost_log) f.cost_log[row * (unsigned long long)f.D + d] = c;
-  }
-  if (f.cost_log) {
-    __syncthreads();  // every thread has read the counter
-    if (threadIdx.x == 0) *f.epoch = *f.epoch + 1;
-  }
-}
-
 // The kernel side the evaluation kernel is instantiated for: LeNet-1's 5, every other one 0.
 inline bool lenet_fast(const LenetGeom& g) { return g.k == 5; }
 
@@ -139,7 +89,8 @@ int lenet_prepare_device() {
   for (int loss : {CFA_LENET_LOSS_XENT, CFA_LENET_LOSS_HUBER})
     for (bool fast : {true, false})  // refused: launches stay within 64 KiB
       (void)raise_lds_limit((const void*)lenet_eval_kernel_for(fast, loss), lim);
-  return lenet_grad_prepare_device();
+  if (int rc = lenet_grad_prepare_device()) return rc;
+  return lenet_max_prepare_device();
 }
 
 extern "C" size_t cfa_lenet_params(int side, int kernel, int c1, int c2, int classes) {
@@ -169,33 +120,11 @@ extern "C" int cfa_lenet_eval_loss_f32(const float* x, size_t x_dev_stride, cons
                                        size_t workspace_bytes, int loss, void* stream) {
   // the messages keep the name callers of either entry know
   const char* fn = loss == CFA_LENET_LOSS_XENT ? "cfa_lenet_eval_f32" : "cfa_lenet_eval_loss_f32";
-  if (loss != CFA_LENET_LOSS_XENT && loss != CFA_LENET_LOSS_HUBER)
-    return fail(CFA_E_INVALID, "%s: unknown loss kind %d (CFA_LENET_LOSS_XENT or CFA_LENET_LOSS_HUBER)", fn, loss);
-  if (!x || !labels || !models || !cost || !workspace) return fail(CFA_E_INVALID, "%s: null buffer", fn);
-  if (D < 1 || batch < 1 || batches < 1 || Nt < 1)
-    return fail(CFA_E_INVALID, "%s: D %d, batch %d, batches %d and Nt %d must be >= 1", fn, D, batch, batches, Nt);
   LenetGeom g;
-  if (!lenet_geom(side, kernel, c1, c2, classes, g))
-    return fail(CFA_E_INVALID, "%s: bad geometry (side %d kernel %d c1 %d c2 %d classes %d): every dimension >= 1 "
-                "and a second pooled map of at least 1 x 1", fn, side, kernel, c1, c2, classes);
-  if ((long long)batch * batches > Nt)
-    return fail(CFA_E_INVALID, "%s: %d batches of %d samples do not fit the %d of the test set", fn, batches, batch,
-                Nt);
-  if ((long long)pitch < g.P)
-    return fail(CFA_E_INVALID, "%s: pitch %zu below the model's %lld parameters", fn, pitch, g.P);
-  const long long set = (long long)Nt * side * side;
-  if ((x_dev_stride != 0 && (long long)x_dev_stride < set) || (label_dev_stride != 0 && (long long)label_dev_stride < Nt))
-    return fail(CFA_E_INVALID, "%s: device strides %zu / %zu below one device's set (%lld / %d)", fn, x_dev_stride,
-                label_dev_stride, set, Nt);
-  if ((cost_log == nullptr) != (epoch == nullptr))
-    return fail(CFA_E_INVALID, "%s: cost_log and epoch are given together or not at all", fn);
-  if (cost_log && log_cap < 1) return fail(CFA_E_INVALID, "%s: log_cap %d must be >= 1", fn, log_cap);
-  if (workspace_bytes < cfa_lenet_eval_workspace_bytes(D, batches))
-    return fail(CFA_E_INVALID, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes,
-                cfa_lenet_eval_workspace_bytes(D, batches));
-  if (ended && !std::isfinite(target)) return fail(CFA_E_INVALID, "%s: target must be finite", fn);
-  if (classes > 64) return fail(CFA_E_UNSUPPORTED, "%s: more than 64 classes", fn);
-  if (D > 65535) return fail(CFA_E_UNSUPPORTED, "%s: more than 65535 devices", fn);
+  if (int rc = lenet_eval_checks(fn, x, labels, x_dev_stride, label_dev_stride, Nt, side, kernel, c1, c2, classes,
+                                 models, pitch, D, batch, batches, target, ended, cost, cost_log, log_cap, epoch,
+                                 workspace, workspace_bytes, cfa_lenet_eval_workspace_bytes(D, batches), loss, g))
+    return rc;
   // the kernel indexes the model and the LDS with ints
   const bool fast = lenet_fast(g);
   const LenetEvalKernel kern = lenet_eval_kernel_for(fast, loss);
@@ -213,6 +142,6 @@ extern "C" int cfa_lenet_eval_loss_f32(const float* x, size_t x_dev_stride, cons
   kern<<<grid, kLenetBlock, (size_t)need, st>>>(a, g);
   if (int rc = check_launch("lenet_eval_kernel")) return rc;
   const LenetFinish f{a.ws, D, batches, skip, target, ended, cost, cost_log, log_cap, epoch};
-  lenet_finish_kernel<<<1, kLenetBlock, 0, st>>>(f);
+  lenet_finish_kernel<<<1, kLenetFinishBlock, 0, st>>>(f);
   return check_launch("lenet_finish_kernel");
 }

@@ -23,19 +23,6 @@ constexpr int kGradBlockL = 256;  // 4 waves; three workgroups of LeNet-1 share 
 constexpr int kGradChunk = 2;     // samples per pass through the phases
 constexpr int kGradGroup = 4;     // samples per workgroup: two chunks
 
-struct LenetGradArgs {
-  const float* x;         // [Nt][side][side], or [D][Nt][side][side] with x_stride
-  const int32_t* labels;  // [Nt], or [D][Nt] with label_stride
-  long long x_stride, label_stride;
-  const float* models;    // [D][pitch]
-  long long pitch;
-  const int32_t* src;      // [D] or null: the row of models device d evaluates
-  const long long* first;  // [D] or null: the first sample of device d's batch
-  const int32_t* skip;     // [D] or null
-  int Nt, batch, D, groups;
-  float* ws;  // [D][groups][P + kGradGroup]: a group's gradient sums, then its samples' losses
-};
-
 // LDS floats of the gradient kernel (the sum is spelled out in cfa_lenet_graph.h).
 inline long long lenet_grad_lds(const LenetGeom& g) {
   const long long n1 = (long long)g.p1 * g.p1 * g.c1, d2 = 4LL * g.p2 * g.p2 * g.c2;
@@ -113,32 +100,6 @@ __global__ __launch_bounds__(kGradBlockL, 3) void lenet_grad_kernel(LenetGradArg
   for (int i = tid; i < kGradGroup; i += T) out[P + i] = i < count ? loss[i] : 0.f;
 }
 
-struct LenetGradFinish {
-  const float* ws;
-  int P, groups, batch;
-  const int32_t* skip;
-  float* grads;  // [D][gpitch]
-  long long gpitch;
-  float* loss;  // [D] or null
-};
-
-// Grid (ceil((P + 1) / block), D): element e < P of device d's row, or e == P, its loss.
-__global__ __launch_bounds__(kGradBlockL) void lenet_grad_finish_kernel(LenetGradFinish f) {
-  const int dv = blockIdx.y;
-  if (f.skip && f.skip[dv]) return;
-  const int e = blockIdx.x * blockDim.x + threadIdx.x, stride = f.P + kGradGroup;
-  const float* base = f.ws + (long long)dv * f.groups * stride;
-  if (e < f.P) {
-    float acc = base[e];
-    for (int gi = 1; gi < f.groups; ++gi) acc += base[(long long)gi * stride + e];
-    f.grads[(long long)dv * f.gpitch + e] = acc / (float)f.batch;
-  } else if (e == f.P && f.loss) {  // reduce_mean over the batch, fp32, in sample order
-    float c = 0.f;
-    for (int s = 0; s < f.batch; ++s) c += base[(long long)(s / kGradGroup) * stride + f.P + s % kGradGroup];
-    f.loss[dv] = c / (float)f.batch;
-  }
-}
-
 inline int lenet_grad_groups(int batch) { return (batch + kGradGroup - 1) / kGradGroup; }
 
 using LenetGradKernel = void (*)(LenetGradArgs, LenetGeom);
@@ -186,28 +147,10 @@ extern "C" int cfa_lenet_grad_loss_f32(const float* x, size_t x_dev_stride, cons
                                        int loss_kind, void* stream) {
   // the messages keep the name callers of either entry know
   const char* fn = loss_kind == CFA_LENET_LOSS_XENT ? "cfa_lenet_grad_f32" : "cfa_lenet_grad_loss_f32";
-  if (loss_kind != CFA_LENET_LOSS_XENT && loss_kind != CFA_LENET_LOSS_HUBER)
-    return fail(CFA_E_INVALID, "%s: unknown loss kind %d (CFA_LENET_LOSS_XENT or CFA_LENET_LOSS_HUBER)", fn,
-                loss_kind);
-  if (!x || !labels || !models || !grads || !workspace) return fail(CFA_E_INVALID, "%s: null buffer", fn);
-  if (D < 1 || batch < 1 || Nt < 1)
-    return fail(CFA_E_INVALID, "%s: D %d, batch %d and Nt %d must be >= 1", fn, D, batch, Nt);
   LenetGeom g;
-  if (!lenet_geom(side, kernel, c1, c2, classes, g))
-    return fail(CFA_E_INVALID, "%s: bad geometry (side %d kernel %d c1 %d c2 %d classes %d): every dimension >= 1 "
-                "and a second pooled map of at least 1 x 1", fn, side, kernel, c1, c2, classes);
-  if (batch > Nt)
-    return fail(CFA_E_INVALID, "%s: a batch of %d samples does not fit the %d of the training set", fn, batch, Nt);
-  if ((long long)pitch < g.P)
-    return fail(CFA_E_INVALID, "%s: pitch %zu below the model's %lld parameters", fn, pitch, g.P);
-  if ((long long)gpitch < g.P)
-    return fail(CFA_E_INVALID, "%s: gpitch %zu below the model's %lld parameters", fn, gpitch, g.P);
-  const long long set = (long long)Nt * side * side;
-  if ((x_dev_stride != 0 && (long long)x_dev_stride < set) || (label_dev_stride != 0 && (long long)label_dev_stride < Nt))
-    return fail(CFA_E_INVALID, "%s: device strides %zu / %zu below one device's set (%lld / %d)", fn, x_dev_stride,
-                label_dev_stride, set, Nt);
-  if (classes > 64) return fail(CFA_E_UNSUPPORTED, "%s: more than 64 classes", fn);
-  if (D > 65535) return fail(CFA_E_UNSUPPORTED, "%s: more than 65535 devices", fn);
+  if (int rc = lenet_grad_checks(fn, x, labels, x_dev_stride, label_dev_stride, Nt, side, kernel, c1, c2, classes, models,
+                                 pitch, D, batch, grads, gpitch, workspace, loss_kind, g))
+    return rc;
   // the kernel indexes the model and the LDS with ints
   const bool fast = g.k == 5;
   const LenetGradKernel kern = lenet_grad_kernel_for(fast, loss_kind);
@@ -226,7 +169,7 @@ extern "C" int cfa_lenet_grad_loss_f32(const float* x, size_t x_dev_stride, cons
   kern<<<grid, kGradBlockL, (size_t)need, st>>>(a, g);
   if (int rc = check_launch("lenet_grad_kernel")) return rc;
   const LenetGradFinish f{a.ws, (int)g.P, groups, batch, skip, grads, (long long)gpitch, loss};
-  const dim3 fgrid((unsigned)((g.P + 1 + kGradBlockL - 1) / kGradBlockL), (unsigned)D);
-  lenet_grad_finish_kernel<<<fgrid, kGradBlockL, 0, st>>>(f);
+  const dim3 fgrid((unsigned)((g.P + 1 + kLenetFinishBlock - 1) / kLenetFinishBlock), (unsigned)D);
+  lenet_grad_finish_kernel<kGradGroup><<<fgrid, kLenetFinishBlock, 0, st>>>(f);
   return check_launch("lenet_grad_finish_kernel");
 }

@@ -89,6 +89,35 @@ inline long long lenet_sample_floats(const LenetGeom& g) {
 
 // ---- phases ---------------------------------------------------------------------------------
 
+// AveragePooling2D of a window's relu(z): summed (0,0) (0,1) (1,0) (1,1) and scaled by 0.25 (exact);
+// bits: bit 2 dy + dx is the test z > 0 of window position (dy, dx).
+struct LenetAvgPool {
+  static __device__ __forceinline__ float pool(float z00, float z01, float z10, float z11, uint8_t& bits) {
+    const float h00 = z00 > 0.f ? z00 : 0.f, h01 = z01 > 0.f ? z01 : 0.f;
+    const float h10 = z10 > 0.f ? z10 : 0.f, h11 = z11 > 0.f ? z11 : 0.f;
+    bits = (uint8_t)((z00 > 0.f ? 1 : 0) | (z01 > 0.f ? 2 : 0) | (z10 > 0.f ? 4 : 0) | (z11 > 0.f ? 8 : 0));
+    return (((h00 + h01) + h10) + h11) * 0.25f;
+  }
+};
+
+// MaxPooling2D of a window's relu(z), and the decision TF's MaxPoolGrad takes again: the FIRST
+// largest relu(z) in window order (0,0) (0,1) (1,0) (1,1) (a later position wins only where it is
+// strictly larger). bits: the position 2 dy + dx in bits 0-1 and its test z > 0 in bit 2; a
+// window without a positive z keeps position 0 with the test clear, so it passes nothing.
+struct LenetMaxPool {
+  static __device__ __forceinline__ float pool(float z00, float z01, float z10, float z11, uint8_t& bits) {
+    const float h00 = z00 > 0.f ? z00 : 0.f, h01 = z01 > 0.f ? z01 : 0.f;
+    const float h10 = z10 > 0.f ? z10 : 0.f, h11 = z11 > 0.f ? z11 : 0.f;
+    float m = h00;
+    int at = 0;
+    if (h01 > m) m = h01, at = 1;
+    if (h10 > m) m = h10, at = 2;
+    if (h11 > m) m = h11, at = 3;
+    bits = (uint8_t)(at | (m > 0.f ? 4 : 0));
+    return m;
+  }
+};
+
 // One stage of the family for ns samples: out[s][py][px][co] = mean over the 2 x 2 window of
 // relu(conv(in)[2py + dy][2px + dx][co] + b[co]), in [ns][sin][sin][cin] and out
 // [ns][pout][pout][cout] both NHWC, W (k, k, cin, cout). The four convolutions of a window run
@@ -97,7 +126,10 @@ inline long long lenet_sample_floats(const LenetGeom& g) {
 // K > 0: the kernel side at compile time (the tap loops unroll, and the window's (K + 1)^2 inputs
 // are loaded once); K = 0: any side. The arithmetic and its order are the same either way.
 // gate (or null): [ns][pout][pout][cout] bytes, bit 2 dy + dx set where z[2py + dy][2px + dx] > 0.
-template <int K>
+// Pool: what a window's four pre-activations become (LenetAvgPool above, or LenetMaxPool, whose
+// pooled value is the window's largest relu(z) and whose byte is LenetMaxGated's); everything up
+// to the bias is the same code for both.
+template <int K, class Pool = LenetAvgPool>
 __device__ __forceinline__ void lenet_conv_pool(float* __restrict__ out, const float* __restrict__ in,
                                                 const float* __restrict__ W, const float* __restrict__ b, int ns,
                                                 int sin, int cin, int cout, int kside, int pout, int tid, int T,
@@ -130,10 +162,9 @@ __device__ __forceinline__ void lenet_conv_pool(float* __restrict__ out, const f
     }
     const float bias = b[co];
     z00 += bias, z01 += bias, z10 += bias, z11 += bias;
-    const float h00 = z00 > 0.f ? z00 : 0.f, h01 = z01 > 0.f ? z01 : 0.f;
-    const float h10 = z10 > 0.f ? z10 : 0.f, h11 = z11 > 0.f ? z11 : 0.f;
-    out[idx] = (((h00 + h01) + h10) + h11) * 0.25f;
-    if (gate) gate[idx] = (uint8_t)((z00 > 0.f ? 1 : 0) | (z01 > 0.f ? 2 : 0) | (z10 > 0.f ? 4 : 0) | (z11 > 0.f ? 8 : 0));
+    uint8_t bits;
+    out[idx] = Pool::pool(z00, z01, z10, z11, bits);
+    if (gate) gate[idx] = bits;
   }
 }
 
@@ -255,6 +286,19 @@ struct LenetGated {
   }
 };
 
+// The max pool's: the whole of d(pooled) to the window's selected position where its z > 0, as a
+// product with 1 or 0 (a NaN upstream reaches every element); gate holds LenetMaxPool's bytes.
+struct LenetMaxGated {
+  const uint8_t* gate;
+  const float* dp;
+  int pout, cout;
+  __device__ __forceinline__ float operator()(int s, int y, int x, int co) const {
+    const int i = ((s * pout + (y >> 1)) * pout + (x >> 1)) * cout + co;
+    const int b = gate[i];
+    return ((b >> 2) & 1 && (b & 3) == 2 * (y & 1) + (x & 1) ? 1.f : 0.f) * dp[i];
+  }
+};
+
 // The same values written out: v [ns][side][side][cout], side = 2 pout.
 struct LenetStored {
   const float* v;
@@ -264,7 +308,8 @@ struct LenetStored {
   }
 };
 
-__device__ __forceinline__ void lenet_store_gated(float* v, const LenetGated& g, int ns, int tid, int T) {
+template <class Gated>
+__device__ __forceinline__ void lenet_store_gated(float* v, const Gated& g, int ns, int tid, int T) {
   const int side = 2 * g.pout;
   for (int idx = tid; idx < ns * side * side * g.cout; idx += T) {
     const int co = idx % g.cout, x = (idx / g.cout) % side, y = (idx / (g.cout * side)) % side;
@@ -372,6 +417,201 @@ __device__ __forceinline__ void lenet_conv_igrad(float* din, const float* dzc, c
       }
     din[idx] = acc;
   }
+}
+
+// lenet_conv_igrad for weights that are NOT in LDS (W in global memory), bit for bit the same
+// sums: tap by tap in (ky, kx) order the tap's [cin][cout] slice is copied (coalesced) into `tile`
+// [cin][cout + 1] floats of LDS (the pad keeps the cin rows a wave reads on different banks), every
+// thread continues the sums it owns over co in order, and keeps them in din between taps (an fp32
+// store and load is exact, so the chain of fmas is lenet_conv_igrad's). One copy of a tap serves
+// all ns samples. Every thread of the workgroup calls it: it holds barriers, two per tap; the
+// caller puts one after it.
+__device__ __forceinline__ void lenet_conv_igrad_tiled(float* din, const float* dzc, const float* W, float* tile,
+                                                       int ns, int sin, int cin, int cout, int k, int pout, int tid,
+                                                       int T) {
+  const int side = 2 * pout, tp = cout + 1, n = ns * sin * sin * cin;
+  for (int idx = tid; idx < n; idx += T) din[idx] = 0.f;
+  for (int ky = 0; ky < k; ++ky)
+    for (int kx = 0; kx < k; ++kx) {
+      __syncthreads();  // the previous tap's readers of the tile
+      const float* w = W + (ky * k + kx) * cin * cout;
+      for (int i = tid; i < cin * cout; i += T) tile[(i / cout) * tp + i % cout] = w[i];
+      __syncthreads();
+      for (int idx = tid; idx < n; idx += T) {
+        const int ci = idx % cin, x = (idx / cin) % sin, y = (idx / (cin * sin)) % sin, s = idx / (cin * sin * sin);
+        const int oy = y - ky, ox = x - kx;
+        if ((unsigned)oy >= (unsigned)side || (unsigned)ox >= (unsigned)side) continue;
+        const float* wt = tile + ci * tp;
+        const float* d = dzc + ((s * side + oy) * side + ox) * cout;
+        float acc = din[idx];
+        for (int co = 0; co < cout; ++co) acc = fmaf(wt[co], d[co], acc);
+        din[idx] = acc;
+      }
+    }
+}
+
+// ---- what the average-pool and the max-pool kernels share around the phases ------------------
+
+constexpr int kLenetFinishBlock = 256;  // the workgroup of both finishing kernels
+
+// The arguments of an evaluation kernel (cfa_lenet.hip, cfa_lenet_max.hip).
+struct LenetArgs {
+  const float* x;         // [Nt][side][side], or [D][Nt][side][side] with x_stride
+  const int32_t* labels;  // [Nt], or [D][Nt] with label_stride
+  long long x_stride, label_stride;
+  const float* models;    // [D][pitch]
+  long long pitch;
+  int batch, batches;
+  const int32_t* skip;    // [D] or null
+  float* ws;              // [D][batches] batch losses
+};
+
+struct LenetFinish {
+  const float* ws;
+  int D, batches;
+  const int32_t* skip;
+  double target;
+  int32_t* ended;  // or null
+  double* cost;
+  double* cost_log;  // or null
+  int log_cap;
+  unsigned long long* epoch;  // or null, with cost_log
+};
+
+// One workgroup. Thread d % T owns device d: its cost, its flag (read before it is written, so
+// skip and ended may be one array) and its log entry.
+__global__ __launch_bounds__(kLenetFinishBlock) void lenet_finish_kernel(LenetFinish f) {
+  unsigned long long row = 0;
+  if (f.cost_log) {
+    const unsigned long long e = *f.epoch, last = (unsigned long long)(f.log_cap - 1);
+    row = e < last ? e : last;
+  }
+  for (int d = threadIdx.x; d < f.D; d += blockDim.x) {
+    double c;
+    if (f.skip && f.skip[d]) {
+      c = f.cost[d];
+    } else {
+      double acc = 0.0;
+      for (int b = 0; b < f.batches; ++b) acc += (double)f.ws[(long long)d * f.batches + b];
+      c = acc / (double)f.batches;
+      f.cost[d] = c;
+      if (f.ended) f.ended[d] = f.ended[d] | (c < f.target ? 1 : 0);
+    }
+    if (f.cost_log) f.cost_log[row * (unsigned long long)f.D + d] = c;
+  }
+  if (f.cost_log) {
+    __syncthreads();  // every thread has read the counter
+    if (threadIdx.x == 0) *f.epoch = *f.epoch + 1;
+  }
+}
+
+// The arguments of a gradient kernel (cfa_lenet_grad.hip, cfa_lenet_max.hip).
+struct LenetGradArgs {
+  const float* x;         // [Nt][side][side], or [D][Nt][side][side] with x_stride
+  const int32_t* labels;  // [Nt], or [D][Nt] with label_stride
+  long long x_stride, label_stride;
+  const float* models;    // [D][pitch]
+  long long pitch;
+  const int32_t* src;      // [D] or null: the row of models device d evaluates
+  const long long* first;  // [D] or null: the first sample of device d's batch
+  const int32_t* skip;     // [D] or null
+  int Nt, batch, D, groups;
+  float* ws;  // [D][groups][P + GROUP]: a group's gradient sums, then its samples' losses
+};
+
+struct LenetGradFinish {
+  const float* ws;
+  int P, groups, batch;
+  const int32_t* skip;
+  float* grads;  // [D][gpitch]
+  long long gpitch;
+  float* loss;  // [D] or null
+};
+
+// Grid (ceil((P + 1) / block), D): element e < P of device d's row, or e == P, its loss. GROUP:
+// the samples of a sample group of the gradient kernel that filled ws.
+template <int GROUP>
+__global__ __launch_bounds__(kLenetFinishBlock) void lenet_grad_finish_kernel(LenetGradFinish f) {
+  const int dv = blockIdx.y;
+  if (f.skip && f.skip[dv]) return;
+  const int e = blockIdx.x * blockDim.x + threadIdx.x, stride = f.P + GROUP;
+  const float* base = f.ws + (long long)dv * f.groups * stride;
+  if (e < f.P) {
+    float acc = base[e];
+    for (int gi = 1; gi < f.groups; ++gi) acc += base[(long long)gi * stride + e];
+    f.grads[(long long)dv * f.gpitch + e] = acc / (float)f.batch;
+  } else if (e == f.P && f.loss) {  // reduce_mean over the batch, fp32, in sample order
+    float c = 0.f;
+    for (int s = 0; s < f.batch; ++s) c += base[(long long)(s / GROUP) * stride + f.P + s % GROUP];
+    f.loss[dv] = c / (float)f.batch;
+  }
+}
+
+// The host checks of an evaluation entry, in the order every entry of the family keeps: the
+// objective first, then CFA_E_INVALID for the arguments (ws_need: the entry's workspace bytes),
+// then CFA_E_UNSUPPORTED for classes and D. What fits LDS is the entry's own check, after these.
+inline int lenet_eval_checks(const char* fn, const void* x, const void* labels, size_t x_dev_stride,
+                             size_t label_dev_stride, int Nt, int side, int kernel, int c1, int c2, int classes,
+                             const void* models, size_t pitch, int D, int batch, int batches, double target,
+                             const void* ended, const void* cost, const void* cost_log, int log_cap,
+                             const void* epoch, const void* workspace, size_t workspace_bytes, size_t ws_need,
+                             int loss, LenetGeom& g) {
+  if (loss != CFA_LENET_LOSS_XENT && loss != CFA_LENET_LOSS_HUBER)
+    return fail(CFA_E_INVALID, "%s: unknown loss kind %d (CFA_LENET_LOSS_XENT or CFA_LENET_LOSS_HUBER)", fn, loss);
+  if (!x || !labels || !models || !cost || !workspace) return fail(CFA_E_INVALID, "%s: null buffer", fn);
+  if (D < 1 || batch < 1 || batches < 1 || Nt < 1)
+    return fail(CFA_E_INVALID, "%s: D %d, batch %d, batches %d and Nt %d must be >= 1", fn, D, batch, batches, Nt);
+  if (!lenet_geom(side, kernel, c1, c2, classes, g))
+    return fail(CFA_E_INVALID, "%s: bad geometry (side %d kernel %d c1 %d c2 %d classes %d): every dimension >= 1 "
+                "and a second pooled map of at least 1 x 1", fn, side, kernel, c1, c2, classes);
+  if ((long long)batch * batches > Nt)
+    return fail(CFA_E_INVALID, "%s: %d batches of %d samples do not fit the %d of the test set", fn, batches, batch,
+                Nt);
+  if ((long long)pitch < g.P)
+    return fail(CFA_E_INVALID, "%s: pitch %zu below the model's %lld parameters", fn, pitch, g.P);
+  const long long set = (long long)Nt * side * side;
+  if ((x_dev_stride != 0 && (long long)x_dev_stride < set) || (label_dev_stride != 0 && (long long)label_dev_stride < Nt))
+    return fail(CFA_E_INVALID, "%s: device strides %zu / %zu below one device's set (%lld / %d)", fn, x_dev_stride,
+                label_dev_stride, set, Nt);
+  if ((cost_log == nullptr) != (epoch == nullptr))
+    return fail(CFA_E_INVALID, "%s: cost_log and epoch are given together or not at all", fn);
+  if (cost_log && log_cap < 1) return fail(CFA_E_INVALID, "%s: log_cap %d must be >= 1", fn, log_cap);
+  if (workspace_bytes < ws_need)
+    return fail(CFA_E_INVALID, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, ws_need);
+  if (ended && !std::isfinite(target)) return fail(CFA_E_INVALID, "%s: target must be finite", fn);
+  if (classes > 64) return fail(CFA_E_UNSUPPORTED, "%s: more than 64 classes", fn);
+  if (D > 65535) return fail(CFA_E_UNSUPPORTED, "%s: more than 65535 devices", fn);
+  return CFA_OK;
+}
+
+// The same for a gradient entry. Its workspace is checked by the entry after what fits LDS, as
+// cfa_lenet_grad_loss_f32 always has.
+inline int lenet_grad_checks(const char* fn, const void* x, const void* labels, size_t x_dev_stride,
+                             size_t label_dev_stride, int Nt, int side, int kernel, int c1, int c2, int classes,
+                             const void* models, size_t pitch, int D, int batch, const void* grads, size_t gpitch,
+                             const void* workspace, int loss_kind, LenetGeom& g) {
+  if (loss_kind != CFA_LENET_LOSS_XENT && loss_kind != CFA_LENET_LOSS_HUBER)
+    return fail(CFA_E_INVALID, "%s: unknown loss kind %d (CFA_LENET_LOSS_XENT or CFA_LENET_LOSS_HUBER)", fn,
+                loss_kind);
+  if (!x || !labels || !models || !grads || !workspace) return fail(CFA_E_INVALID, "%s: null buffer", fn);
+  if (D < 1 || batch < 1 || Nt < 1)
+    return fail(CFA_E_INVALID, "%s: D %d, batch %d and Nt %d must be >= 1", fn, D, batch, Nt);
+  if (!lenet_geom(side, kernel, c1, c2, classes, g))
+    return fail(CFA_E_INVALID, "%s: bad geometry (side %d kernel %d c1 %d c2 %d classes %d): every dimension >= 1 "
+                "and a second pooled map of at least 1 x 1", fn, side, kernel, c1, c2, classes);
+  if (batch > Nt)
+    return fail(CFA_E_INVALID, "%s: a batch of %d samples does not fit the %d of the training set", fn, batch, Nt);
+  if ((long long)pitch < g.P)
+    return fail(CFA_E_INVALID, "%s: pitch %zu below the model's %lld parameters", fn, pitch, g.P);
+  if ((long long)gpitch < g.P)
+    return fail(CFA_E_INVALID, "%s: gpitch %zu below the model's %lld parameters", fn, gpitch, g.P);
+  const long long set = (long long)Nt * side * side;
+  if ((x_dev_stride != 0 && (long long)x_dev_stride < set) || (label_dev_stride != 0 && (long long)label_dev_stride < Nt))
+    return fail(CFA_E_INVALID, "%s: device strides %zu / %zu below one device's set (%lld / %d)", fn, x_dev_stride,
+                label_dev_stride, set, Nt);
+  if (classes > 64) return fail(CFA_E_UNSUPPORTED, "%s: more than 64 classes", fn);
+  if (D > 65535) return fail(CFA_E_UNSUPPORTED, "%s: more than 65535 devices", fn);
+  return CFA_OK;
 }
 
 }  // namespace

@@ -558,16 +558,18 @@ class Engine:
         """Parameters of a LeNet-family model (cfa_lenet_params); 0 for a geometry without one."""
         return int(_lib.load().cfa_lenet_params(*(int(v) for v in geom)))
 
-    def lenet_workspace(self, D: int, batches: int) -> torch.Tensor:
-        """Workspace of the batch losses (cfa_lenet_eval_workspace_bytes)."""
-        n = int(_lib.load().cfa_lenet_eval_workspace_bytes(int(D), int(batches)))
+    def lenet_workspace(self, D: int, batches: int, pool: str = "avg") -> torch.Tensor:
+        """Workspace of the batch losses (cfa_lenet_eval_workspace_bytes, or cfa_lenet_max_eval_workspace_bytes
+        for ``pool="max"``)."""
+        fn = getattr(_lib.load(), f"cfa_lenet_{_lib.lenet_pool(pool)}eval_workspace_bytes")
+        n = int(fn(int(D), int(batches)))
         return torch.empty(max(n // 4, 1), dtype=torch.float32, device=self.device)
 
     def lenet_eval(self, geom: Sequence[int], x: torch.Tensor, labels: torch.Tensor, models: torch.Tensor,
                    batch: int, batches: int, cost: torch.Tensor, workspace: torch.Tensor,
                    skip: Optional[torch.Tensor] = None, target: float = 0.0, ended: Optional[torch.Tensor] = None,
                    cost_log: Optional[torch.Tensor] = None, epoch: Optional[torch.Tensor] = None,
-                   stream=None, loss: str = "xent") -> torch.Tensor:
+                   stream=None, loss: str = "xent", pool: str = "avg") -> torch.Tensor:
         """cfa_lenet_eval_loss_f32: the validation cost of every device of ``models`` [D, P] (fp32 CUDA,
         unit element stride, any row pitch, read only; get_weights() order) on the LeNet-family
         ``geom`` = (side, kernel, c1, c2, classes), over ``batches`` batches of ``batch`` samples
@@ -579,9 +581,11 @@ class Engine:
         [cap, D] fp64 CUDA and ``epoch`` (one-element int64 CUDA counter), given together: as
         ``local_sgd``. ``workspace``: ``lenet_workspace(D, batches)``. ``loss``: "xent" (the
         cross-entropy drivers' objective) or "huber" (the Huber drivers': Huber(label,
-        softmax(z)[label])); ValueError for any other, before any device call. The library
-        validates the rest (CFAError)."""
-        kind = _lib.lenet_loss_kind(loss)
+        softmax(z)[label])); ValueError for any other, before any device call. ``pool``: "avg"
+        (LeNet-1's AveragePooling2D) or "max" (cfa_lenet_max_eval_loss_f32: the drivers' max-pool
+        CNNs, ``workspace`` from ``lenet_workspace(D, batches, "max")``); ValueError for any
+        other. The library validates the rest (CFAError)."""
+        kind, infix = _lib.lenet_loss_kind(loss), _lib.lenet_pool(pool)
         geom = tuple(int(v) for v in geom)
         if len(geom) != 5:
             raise ValueError("geom must be (side, kernel, c1, c2, classes)")
@@ -621,7 +625,7 @@ class Engine:
         pitch = int(models.stride(0)) if D > 1 else P
         if pitch < P:
             raise ValueError("models rows overlap (pitch below P)")
-        _lib.call("cfa_lenet_eval_loss_f32", x.data_ptr(), x_stride, labels.data_ptr(), label_stride, Nt, *geom,
+        _lib.call(f"cfa_lenet_{infix}eval_loss_f32", x.data_ptr(), x_stride, labels.data_ptr(), label_stride, Nt, *geom,
                   models.data_ptr(), pitch, D, batch, batches, skip.data_ptr() if skip is not None else None,
                   float(target), ended.data_ptr() if ended is not None else None, cost.data_ptr(),
                   cost_log.data_ptr() if cost_log is not None else None, cap,
@@ -630,15 +634,18 @@ class Engine:
         return cost
 
     # -- minibatch gradient of a TF2 LeNet-1 population ---------------------------------------
-    def lenet_grad_workspace(self, D: int, batch: int, geom: Sequence[int]) -> torch.Tensor:
-        """Workspace of the sample groups' partial gradients (cfa_lenet_grad_workspace_bytes)."""
-        n = int(_lib.load().cfa_lenet_grad_workspace_bytes(int(D), int(batch), *(int(v) for v in geom)))
+    def lenet_grad_workspace(self, D: int, batch: int, geom: Sequence[int], pool: str = "avg") -> torch.Tensor:
+        """Workspace of the sample groups' partial gradients (cfa_lenet_grad_workspace_bytes, or
+        cfa_lenet_max_grad_workspace_bytes for ``pool="max"``)."""
+        fn = getattr(_lib.load(), f"cfa_lenet_{_lib.lenet_pool(pool)}grad_workspace_bytes")
+        n = int(fn(int(D), int(batch), *(int(v) for v in geom)))
         return torch.empty(max(n // 4, 1), dtype=torch.float32, device=self.device)
 
     def lenet_grad(self, geom: Sequence[int], x: torch.Tensor, labels: torch.Tensor, models: torch.Tensor,
                    batch: int, grads: torch.Tensor, workspace: torch.Tensor, loss: Optional[torch.Tensor] = None,
                    src: Optional[torch.Tensor] = None, first: Optional[torch.Tensor] = None,
-                   skip: Optional[torch.Tensor] = None, stream=None, loss_kind: str = "xent") -> torch.Tensor:
+                   skip: Optional[torch.Tensor] = None, stream=None, loss_kind: str = "xent",
+                   pool: str = "avg") -> torch.Tensor:
         """cfa_lenet_grad_loss_f32: the mean loss and its gradient over one batch of ``batch`` samples
         for every device of ``models`` [D, P] (fp32 CUDA, unit element stride, any row pitch, read
         only) on the LeNet-family ``geom``, with the training set ``x`` [Nt, side, side] fp32 /
@@ -651,9 +658,11 @@ class Engine:
         ``skip`` ([D] int32 CUDA, or None): a flagged device's row and loss are not touched.
         ``workspace``: ``lenet_grad_workspace(D, batch, geom)``. ``loss_kind``: the objective,
         "xent" or "huber" as ``lenet_eval``'s ``loss`` (here ``loss`` is the output buffer);
-        ValueError for any other, before any device call. The library validates the rest
+        ValueError for any other, before any device call. ``pool``: "avg" or "max" as
+        ``lenet_eval``'s (cfa_lenet_max_grad_loss_f32, ``workspace`` from
+        ``lenet_grad_workspace(D, batch, geom, "max")``). The library validates the rest
         (CFAError)."""
-        kind = _lib.lenet_loss_kind(loss_kind)
+        kind, infix = _lib.lenet_loss_kind(loss_kind), _lib.lenet_pool(pool)
         geom = tuple(int(v) for v in geom)
         if len(geom) != 5:
             raise ValueError("geom must be (side, kernel, c1, c2, classes)")
@@ -690,7 +699,7 @@ class Engine:
         if pitch < P or gpitch < P:
             raise ValueError("models or grads rows overlap (pitch below P)")
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        _lib.call("cfa_lenet_grad_loss_f32", x.data_ptr(), x_stride, labels.data_ptr(), label_stride, Nt, *geom,
+        _lib.call(f"cfa_lenet_{infix}grad_loss_f32", x.data_ptr(), x_stride, labels.data_ptr(), label_stride, Nt, *geom,
                   models.data_ptr(), pitch, D, ptr(src), ptr(first), batch, ptr(skip), grads.data_ptr(), gpitch,
                   ptr(loss), workspace.data_ptr(), workspace.numel() * 4, kind, self.stream_handle(stream))
         return grads

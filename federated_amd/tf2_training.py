@@ -10,7 +10,8 @@ train on ``keras.losses.Huber()`` between the label and the true class's probabi
 (``federated_learning_keras_consensus_FL_MNIST.py:369-377``): ``loss="huber"``. ``LenetTraining`` holds what those steps need (the
 training set, the batch size, each device's position in its set, the gradient and loss buffers)
 and computes all D gradients in one ``cfa_lenet_grad_loss_f32`` call, for the model family, geometry and
-row layout of ``tf2_validation`` (``lenet_layer_shapes``). With ``PopulationOptimizer`` and
+row layout of ``tf2_validation`` (``lenet_layer_shapes``); ``pool="max"`` serves the drivers'
+max-pool CNNs (``MNIST_CNN32``, ``MNIST_CNN14``) through ``cfa_lenet_max_grad_loss_f32``. With ``PopulationOptimizer`` and
 ``LenetValidation`` one epoch of a population stays on the device::
 
     val.validate(pop.models, skip=pop.ended, ended=pop.ended)
@@ -27,11 +28,11 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from ._lib import lenet_loss_kind
+from ._lib import lenet_loss_kind, lenet_pool
 
-from .tf2_validation import LENET1, MAX_CLASSES, _stages, lenet_layer_shapes, lenet_size
+from .tf2_validation import LENET1, MAX_CLASSES, MNIST_CNN14, MNIST_CNN32, _stages, lenet_layer_shapes, lenet_size
 
-__all__ = ["LenetTraining", "lenet_size", "lenet_layer_shapes", "LENET1"]
+__all__ = ["LenetTraining", "lenet_size", "lenet_layer_shapes", "LENET1", "MNIST_CNN32", "MNIST_CNN14"]
 
 
 class LenetTraining:
@@ -40,7 +41,7 @@ class LenetTraining:
     @staticmethod
     def check(geom: Sequence[int], x_shape: Sequence[int], labels_shape: Sequence[int], batch: int,
               labels: Optional[np.ndarray] = None, src: Optional[np.ndarray] = None,
-              D: Optional[int] = None, loss: str = "xent") -> dict:
+              D: Optional[int] = None, loss: str = "xent", pool: str = "avg") -> dict:
         """The host half: validates geometry, shapes and the batch without touching a device and
         returns geom, P, Nt, batch and per_device (D, or 0 for the shared set). ``x_shape`` is
         [Nt, side, side] (the set all devices share) or [D, Nt, side, side], and ``labels_shape``
@@ -48,9 +49,10 @@ class LenetTraining:
         ``src`` (a host array, optional; needs ``D`` or a per-device set) to be one integer per
         device in [0, D). ValueError for a geometry without a model (p2 < 1) or with more than
         64 classes, mismatched shapes, ``batch`` below 1 or above Nt, a label or a ``src`` out of
-        range, a ``D`` that disagrees with a per-device set and a ``loss`` other than "xent" or
-        "huber" (the plan is the same for both)."""
+        range, a ``D`` that disagrees with a per-device set, a ``loss`` other than "xent" or
+        "huber" (the plan is the same for both) and a ``pool`` other than "avg" or "max"."""
         lenet_loss_kind(loss)
+        lenet_pool(pool)
         side, k, c1, c2, classes, _ = _stages(geom)
         if classes > MAX_CLASSES:
             raise ValueError(f"more than {MAX_CLASSES} classes")
@@ -83,7 +85,7 @@ class LenetTraining:
                 "per_device": per_device}
 
     def __init__(self, engine, geom: Sequence[int], x_train: torch.Tensor, labels: torch.Tensor, batch: int,
-                 loss: str = "xent"):
+                 loss: str = "xent", pool: str = "avg"):
         """``x_train`` [Nt, side, side] fp32 / ``labels`` [Nt] int32 (contiguous CUDA): the
         training set every device draws its batches from, or [D, Nt, side, side] / [D, Nt] with
         one set per device (the drivers' case). The labels are checked once, here, to lie in
@@ -91,9 +93,10 @@ class LenetTraining:
         "xent" (``*_crossentropy*``) or "huber" (the others, e.g.
         ``federated_learning_keras_consensus_FL_MNIST.py:369-377``: ``keras.losses.Huber()``
         between the integer label itself and the softmax probability of the true class); it is
-        kept as ``loss_kind`` (``loss`` is the buffer of the batch losses)."""
-        info = self.check(geom, x_train.shape, labels.shape, batch, loss=loss)
-        self.engine, self.geom, self.P, self.loss_kind = engine, info["geom"], info["P"], loss
+        kept as ``loss_kind`` (``loss`` is the buffer of the batch losses). ``pool``: "avg"
+        (LeNet-1) or "max" (``MNIST_CNN32``, ``MNIST_CNN14``)."""
+        info = self.check(geom, x_train.shape, labels.shape, batch, loss=loss, pool=pool)
+        self.engine, self.geom, self.P, self.loss_kind, self.pool = engine, info["geom"], info["P"], loss, pool
         self.x_train, self.labels = x_train, labels
         self.Nt, self.batch, self.per_device = info["Nt"], info["batch"], info["per_device"]
         if labels.dtype != torch.int32 or not labels.is_cuda:
@@ -120,7 +123,7 @@ class LenetTraining:
         self.grads = torch.zeros(D, (self.P + 3) // 4 * 4, dtype=torch.float32, device=dev)[:, :self.P]
         self.loss = torch.zeros(D, dtype=torch.float32, device=dev)
         self.cursor = torch.zeros(D, dtype=torch.int64, device=dev)
-        self.workspace = self.engine.lenet_grad_workspace(D, self.batch, self.geom)
+        self.workspace = self.engine.lenet_grad_workspace(D, self.batch, self.geom, self.pool)
         return self
 
     def gradients(self, models: torch.Tensor, src=None, skip: Optional[torch.Tensor] = None,
@@ -143,7 +146,7 @@ class LenetTraining:
         return self.engine.lenet_grad(self.geom, self.x_train, self.labels, models, self.batch,
                                       self.grads if out is None else out, self.workspace, self.loss, src,
                                       self.cursor if first is None else first, skip, stream,
-                                      loss_kind=self.loss_kind)
+                                      loss_kind=self.loss_kind, pool=self.pool)
 
     def advance(self, skip: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``cursor[d] = (cursor[d] + batch) % Nt`` for every device not flagged in ``skip``, on

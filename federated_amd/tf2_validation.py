@@ -17,7 +17,10 @@ The model family is the "LeNet-1 family" ``geom = (side, kernel, c1, c2, classes
                     -> Conv2D(c2, kernel, valid, relu) -> AveragePooling2D(2)
                     -> Flatten -> Dense(classes, softmax)
 
-with a model row in ``get_weights()`` order (``lenet_layer_shapes``), the row layout
+or, with ``pool="max"``, the same chain with ``MaxPooling2D(2)`` in both places: the drivers'
+other two models, ``MNIST_CNN32`` (``-modelselection 1``) and ``MNIST_CNN14`` (any other value),
+through ``cfa_lenet_max_eval_loss_f32``, whose kernels read the model from global memory instead
+of holding it in LDS. A model row is in ``get_weights()`` order (``lenet_layer_shapes``), the row layout
 ``PopulationOptimizer`` and the populations already use. The populations are not edited; the
 chain of one epoch is::
 
@@ -36,11 +39,13 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from ._lib import lenet_loss_kind
+from ._lib import lenet_loss_kind, lenet_pool
 
-__all__ = ["LenetValidation", "lenet_size", "lenet_layer_shapes", "LENET1"]
+__all__ = ["LenetValidation", "lenet_size", "lenet_layer_shapes", "LENET1", "MNIST_CNN32", "MNIST_CNN14"]
 
-LENET1 = (28, 5, 4, 8, 10)  # create_q_model, condition 0
+LENET1 = (28, 5, 4, 8, 10)        # create_q_model, condition 0: pool="avg"
+MNIST_CNN32 = (28, 3, 32, 64, 10)  # condition 1 (``:170-182``), 34 826 parameters: pool="max"
+MNIST_CNN14 = (28, 3, 14, 64, 10)  # any other -modelselection, 24 278 parameters: pool="max"
 MAX_CLASSES = 64            # the library's limit (CFA_E_UNSUPPORTED beyond)
 
 
@@ -78,7 +83,7 @@ class LenetValidation:
     @staticmethod
     def check(geom: Sequence[int], x_shape: Sequence[int], labels_shape: Sequence[int], batch: int,
               batches: Optional[int] = None, target: Optional[float] = None, log_cap: int = 0,
-              labels: Optional[np.ndarray] = None, loss: str = "xent") -> dict:
+              labels: Optional[np.ndarray] = None, loss: str = "xent", pool: str = "avg") -> dict:
         """The host half: validates geometry, shapes and batching without touching a device and
         returns geom, P, Nt, batch, batches, per_device (D, or 0 for the shared set) and target.
         ``x_shape`` is [Nt, side, side] (the set all devices share) or [D, Nt, side, side], and
@@ -86,8 +91,10 @@ class LenetValidation:
         ``labels`` (a host array, optional) is checked to lie in [0, classes). ValueError for a
         geometry without a model (p2 < 1) or with more than 64 classes, mismatched shapes,
         ``batch * batches > Nt``, a non-finite target, a negative ``log_cap``, a label out of
-        range and a ``loss`` other than "xent" or "huber" (the plan is the same for both)."""
+        range, a ``loss`` other than "xent" or "huber" (the plan is the same for both) and a
+        ``pool`` other than "avg" or "max"."""
         lenet_loss_kind(loss)
+        lenet_pool(pool)
         side, k, c1, c2, classes, _ = _stages(geom)
         if classes > MAX_CLASSES:
             raise ValueError(f"more than {MAX_CLASSES} classes")
@@ -118,7 +125,7 @@ class LenetValidation:
 
     def __init__(self, engine, geom: Sequence[int], x_test: torch.Tensor, labels: torch.Tensor, batch: int,
                  batches: Optional[int] = None, target: Optional[float] = None, log_cap: int = 0,
-                 loss: str = "xent"):
+                 loss: str = "xent", pool: str = "avg"):
         """``x_test`` [Nt, side, side] fp32 / ``labels`` [Nt] int32 (contiguous CUDA): the test
         set every device validates on, or [D, Nt, side, side] / [D, Nt] with one set per device.
         ``target``: the driver's ``target_loss``, needed to raise flags. ``log_cap`` > 0 keeps a
@@ -127,9 +134,10 @@ class LenetValidation:
         synchronises). ``loss``: the drivers' objective, "xent" (``*_crossentropy*``:
         ``-log softmax(z)[label]``) or "huber" (the others, e.g.
         ``federated_learning_keras_consensus_FL_MNIST.py:481-483``: ``keras.losses.Huber()``
-        between the integer label itself and the softmax probability of the true class)."""
-        info = self.check(geom, x_test.shape, labels.shape, batch, batches, target, log_cap, loss=loss)
-        self.engine, self.geom, self.P, self.loss_kind = engine, info["geom"], info["P"], loss
+        between the integer label itself and the softmax probability of the true class).
+        ``pool``: "avg" (LeNet-1) or "max" (``MNIST_CNN32``, ``MNIST_CNN14``)."""
+        info = self.check(geom, x_test.shape, labels.shape, batch, batches, target, log_cap, loss=loss, pool=pool)
+        self.engine, self.geom, self.P, self.loss_kind, self.pool = engine, info["geom"], info["P"], loss, pool
         self.x_test, self.labels = x_test, labels
         self.Nt, self.batch, self.batches, self.target = info["Nt"], info["batch"], info["batches"], info["target"]
         self.per_device, self.log_cap = info["per_device"], int(log_cap)
@@ -149,7 +157,7 @@ class LenetValidation:
         self.D = D
         self.val_cost = torch.zeros(D, dtype=torch.float64, device=dev)
         self.val_log = torch.zeros(self.log_cap, D, dtype=torch.float64, device=dev) if self.log_cap > 0 else None
-        self.workspace = self.engine.lenet_workspace(D, self.batches)
+        self.workspace = self.engine.lenet_workspace(D, self.batches, self.pool)
 
     def allocate(self, D: int) -> "LenetValidation":
         """Allocates ``val_cost`` [D] fp64, ``val_log`` and the workspace for D devices now (the
@@ -180,4 +188,4 @@ class LenetValidation:
         return self.engine.lenet_eval(self.geom, self.x_test, self.labels, models, self.batch, self.batches,
                                       self.val_cost, self.workspace, skip, self.target or 0.0, ended,
                                       self.val_log, self.epoch_counter if logged else None, stream,
-                                      loss=self.loss_kind)
+                                      loss=self.loss_kind, pool=self.pool)

@@ -782,6 +782,62 @@ CFA_API int cfa_lenet_grad_loss_f32(const float* x, size_t x_dev_stride, const i
                                     float* grads, size_t gpitch, float* loss,
                                     void* workspace, size_t workspace_bytes, int loss_kind, void* stream);
 
+/* (TF2 drivers) The same two passes for create_q_model's MAX-POOL CNNs, conditions 1 and 2 of
+ * -modelselection (..._MNIST_crossentropy_gradients_exchange.py:170-182 for the model; :321-337 the
+ * local update, :360-385 the gradient at a neighbour's model, :430-455 the validation pass):
+ *   x [side, side, 1] -> Conv2D(c1, kernel x kernel, valid, relu) -> MaxPooling2D(2 x 2, stride 2, valid)
+ *     -> Conv2D(c2, kernel x kernel, valid, relu) -> MaxPooling2D(2 x 2) -> Flatten (NHWC)
+ *     -> Dense(classes, softmax)
+ * with (28, 3, 32, 64, 10), P = 34826, for condition 1 and (28, 3, 14, 64, 10), P = 24278, for any
+ * other value (28 -> 26 -> 13 -> 11 -> 5, flat = 1600: the second pool drops a row and a column).
+ * Geometry, row layout, P (cfa_lenet_params), the cross-correlation, the bias added last, the
+ * z > 0 relu gate, both objectives, the log-softmax form, NaN for a label outside [0, classes)
+ * and every argument are those of cfa_lenet_eval_loss_f32 / cfa_lenet_grad_loss_f32; the argument
+ * lists are theirs. What differs:
+ *   forward:  pooled = max over the window of relu(z); an odd last row and column are dropped.
+ *   backward: the whole of d(pooled) goes to ONE position of the window, the FIRST maximum of
+ *             relu(z) in window order (0,0), (0,1), (1,0), (1,1) (TF's MaxPoolGrad), and then
+ *             through that position's relu gate: a window whose maximum is 0 passes nothing,
+ *             wherever its tie falls. A dropped row or column receives 0. The decision is kept as
+ *             one byte per pooled element (position and gate bit) and applied as a product with
+ *             1 or 0, so a NaN upstream (a label out of range) reaches the device's whole row.
+ * The model is NOT held in LDS: weights are read from global memory (a [D, P] stack stays in L2 /
+ * the Infinity Cache); LDS holds a chunk's activations, their gradients and the decisions, the
+ * chunk sized from the geometry and the device's LDS. Every operation is fp32 (explicit fma, no
+ * contraction, no matrix instructions).
+ * Deterministic, no atomics: every sum has a fixed order that depends on the geometry and the
+ * batch alone (a sample's sums are its own; the gradient kernel adds samples in order within
+ * groups of 8 and the groups in order), so a device's cost, loss and gradient row have the same
+ * bits alone or in a population, whatever D, skip, src, first or the GPU's CU count and LDS
+ * are, and the loss of the gradient call is bit for bit the batch loss of the validation call on
+ * the same samples. No host read, allocation or attribute call after cfa_device_prepare:
+ * capture-safe. Two launches per call.
+ * workspace: at least cfa_lenet_max_eval_workspace_bytes(D, batches) (the fp32 batch losses) or
+ * cfa_lenet_max_grad_workspace_bytes(D, batch, geometry) bytes of DEVICE memory (the groups'
+ * gradient sums: D * ceil(batch / 8) * (P + 8) floats; 0 for D, batch(es) < 1 or a geometry
+ * without a model).
+ * Errors, in the siblings' order: CFA_E_INVALID for an unknown loss (checked first, before any
+ * buffer), then for a null buffer, D, batch, batches or Nt < 1, a bad geometry, batch*batches > Nt
+ * (batch > Nt), pitch or gpitch < P, a short device stride, only one of cost_log / epoch, a
+ * workspace too small, a non-finite target with ended; CFA_E_UNSUPPORTED for classes > 64,
+ * D > 65535, and only then for ONE sample's state beyond a workgroup's LDS (validation: image,
+ * two pooled maps, logits and the batch's losses; gradient: those, their gradients and the gated
+ * map of stage 2). The average-pool entries above keep refusing these geometries. */
+CFA_API size_t cfa_lenet_max_eval_workspace_bytes(int D, int batches);
+CFA_API int cfa_lenet_max_eval_loss_f32(const float* x, size_t x_dev_stride, const int32_t* labels,
+                                        size_t label_dev_stride, int Nt, int side, int kernel, int c1, int c2,
+                                        int classes, const float* models, size_t pitch, int D, int batch, int batches,
+                                        const int32_t* skip, double target, int32_t* ended,
+                                        double* cost, double* cost_log, int log_cap, unsigned long long* epoch,
+                                        void* workspace, size_t workspace_bytes, int loss, void* stream);
+CFA_API size_t cfa_lenet_max_grad_workspace_bytes(int D, int batch, int side, int kernel, int c1, int c2, int classes);
+CFA_API int cfa_lenet_max_grad_loss_f32(const float* x, size_t x_dev_stride, const int32_t* labels,
+                                        size_t label_dev_stride, int Nt, int side, int kernel, int c1, int c2,
+                                        int classes, const float* models, size_t pitch, int D, const int32_t* src,
+                                        const long long* first, int batch, const int32_t* skip,
+                                        float* grads, size_t gpitch, float* loss,
+                                        void* workspace, size_t workspace_bytes, int loss_kind, void* stream);
+
 /* (a1-a6 batched) Population round: one launch mixes D devices.
  * For device d, CSR entries e in [csr_ptr[d], csr_ptr[d+1]) list its sources in order; the
  * FIRST entry is the device's own (local) bucket. Source e is src_ptrs[csr_idx[e]], output d
