@@ -58,6 +58,23 @@ def lenet_pool(pool) -> str:
         raise ValueError(f"pool must be one of {list(LENET_POOLS)}, got {pool!r}")
     return "" if pool == "avg" else "max_"
 
+
+def lenet_family(geom, pool) -> tuple:
+    """(geom as ints, entry-point infix, an image's shape) of a LeNet-family geometry: five numbers
+    (side, kernel, c1, c2, classes) with ``pool``, images [side, side]; or seven (side, channels,
+    kernel, c1, c2, hidden, classes), the hidden-layer family (cfa_lenet_hidden_*), images
+    [side, side, channels], average pool only. ValueError for another ``pool``, another length,
+    and seven numbers with ``pool="max"`` (the drivers build no such model)."""
+    infix = lenet_pool(pool)
+    geom = tuple(int(v) for v in geom)
+    if len(geom) == 7:
+        if pool != "avg":
+            raise ValueError('a seven-number geometry has pool="avg" (the drivers build no such max-pool model)')
+        return geom, "hidden_", (geom[0], geom[0], geom[1])
+    if len(geom) != 5:
+        raise ValueError("geom must be (side, kernel, c1, c2, classes)")
+    return geom, infix, (geom[0], geom[0])
+
 COMPRESS_NONE = 0
 COMPRESS_SPARSE = 1
 COMPRESS_SPARSE_DPCM = 2
@@ -191,6 +208,18 @@ SIGNATURES = {
                                              _c_int, _c_int, _c_int, _c_void_p, _c_size_t, _c_int, _c_void_p,
                                              _c_void_p, _c_int, _c_void_p, _c_void_p, _c_size_t, _c_void_p,
                                              _c_void_p, _c_size_t, _c_int, _c_void_p]),
+    "cfa_lenet_hidden_params": (_c_size_t, [_c_int] * 7),
+    "cfa_lenet_hidden_eval_workspace_bytes": (_c_size_t, [_c_int, _c_int]),
+    "cfa_lenet_hidden_eval_loss_f32": (_c_int, [_c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_int, _c_int, _c_int,
+                                                _c_int, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_size_t, _c_int,
+                                                _c_int, _c_int, _c_void_p, ctypes.c_double, _c_void_p, _c_void_p,
+                                                _c_void_p, _c_int, _c_void_p, _c_void_p, _c_size_t, _c_int,
+                                                _c_void_p]),
+    "cfa_lenet_hidden_grad_workspace_bytes": (_c_size_t, [_c_int] * 9),
+    "cfa_lenet_hidden_grad_loss_f32": (_c_int, [_c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_int, _c_int, _c_int,
+                                                _c_int, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_size_t, _c_int,
+                                                _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_size_t,
+                                                _c_void_p, _c_void_p, _c_size_t, _c_int, _c_void_p]),
     "cfa_optim_tile": (_c_int, []),
     "cfa_optim_workspace_bytes": (_c_size_t, [_c_int, _c_size_t, _c_int]),
     "cfa_optim_step_f32": (_c_int, [_c_void_p, _c_size_t, _c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t,

@@ -41,14 +41,19 @@ __device__ __forceinline__ void stage(float* dst, const float* src, int n, int t
 
 constexpr int kMaxTaps = 32;  // conv filter taps held in registers (larger filters read LDS)
 
+// Kernels of one translation unit whose granted limit raise_lds_limit remembers. A kernel beyond
+// them gets no slot and asks the runtime again at every launch above 64 KiB, which a capture must
+// not do: a file's kernel table static_asserts its size against this.
+constexpr int kLdsLimitSlots = 8;
+
 // Raise a kernel's dynamic-LDS limit to `bytes` once per (kernel, device); false if refused.
 bool raise_lds_limit(const void* kernel, int bytes) {
-  static const void* keys[8] = {nullptr};
-  static int granted[8][64] = {{0}};  // per kernel slot and device: the limit granted so far
+  static const void* keys[kLdsLimitSlots] = {nullptr};
+  static int granted[kLdsLimitSlots][64] = {{0}};  // per kernel slot and device: the limit granted so far
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
   int slot = -1;
-  for (int i = 0; i < 8 && dev >= 0; ++i) {
+  for (int i = 0; i < kLdsLimitSlots && dev >= 0; ++i) {
     const void* k = __atomic_load_n(&keys[i], __ATOMIC_ACQUIRE);
     if (k == kernel) { slot = i; break; }
     if (!k) {

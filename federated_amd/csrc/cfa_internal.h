@@ -136,6 +136,8 @@ int lenet_prepare_device();
 int lenet_grad_prepare_device();
 // cfa_lenet_max.hip: the max-pool kernels of the same family (called by lenet_prepare_device).
 int lenet_max_prepare_device();
+// cfa_lenet_hidden.hip: the hidden-layer kernels of the same family (called by lenet_prepare_device).
+int lenet_hidden_prepare_device();
 // cfa_ring.hip: the sliding ring round's seam kernels (those that keep more than 64 KiB of rows).
 int ring_prepare_device();
 // cfa_population.hip: one-thread launch that leaves a device counter (a schedule's round, a cost

@@ -90,7 +90,8 @@ int lenet_prepare_device() {
     for (bool fast : {true, false})  // refused: launches stay within 64 KiB
       (void)raise_lds_limit((const void*)lenet_eval_kernel_for(fast, loss), lim);
   if (int rc = lenet_grad_prepare_device()) return rc;
-  return lenet_max_prepare_device();
+  if (int rc = lenet_max_prepare_device()) return rc;
+  return lenet_hidden_prepare_device();
 }
 
 extern "C" size_t cfa_lenet_params(int side, int kernel, int c1, int c2, int classes) {

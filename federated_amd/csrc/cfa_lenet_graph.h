@@ -87,6 +87,64 @@ inline long long lenet_sample_floats(const LenetGeom& g) {
   return (long long)g.side * g.side + (long long)g.p1 * g.p1 * g.c1 + g.flat + g.C;
 }
 
+// The family with an input of `cin` channels and a hidden dense layer (cfa_lenet_hidden.hip: the
+// CIFAR drivers' -modelselection 1), from the caller's seven numbers:
+//   x [side, side, cin] -> Conv2D(c1) -> relu -> AveragePooling2D -> Conv2D(c2) -> relu -> AveragePooling2D
+//     -> Flatten -> Dense(H, relu) -> Dense(classes)
+// A model row is K1 (k, k, cin, c1) b1 K2 (k, k, c1, c2) b2 Wh (flat, H) bh Wd (H, classes) bd.
+struct LenetHiddenGeom {
+  int side, cin, k, c1, c2, H, C;
+  int s1, p1, s2, p2;
+  int flat;
+  int oK1, ob1, oK2, ob2, oWh, obh, oWd, obd;
+  long long P;
+};
+
+// false for a geometry that has no model: a dimension < 1 (hidden included), a kernel larger than
+// its input, an empty pooled map. Offsets are valid only while P fits an int, as lenet_geom's.
+inline bool lenet_hidden_geom(int side, int channels, int kernel, int c1, int c2, int hidden, int classes,
+                              LenetHiddenGeom& g) {
+  if (side < 1 || channels < 1 || kernel < 1 || c1 < 1 || c2 < 1 || hidden < 1 || classes < 1) return false;
+  g.side = side, g.cin = channels, g.k = kernel, g.c1 = c1, g.c2 = c2, g.H = hidden, g.C = classes;
+  g.s1 = side - kernel + 1;
+  g.p1 = g.s1 > 0 ? g.s1 / 2 : 0;
+  g.s2 = g.p1 - kernel + 1;
+  g.p2 = g.s2 > 0 ? g.s2 / 2 : 0;
+  if (g.p2 < 1) return false;
+  const long long kk = (long long)kernel * kernel, flat = (long long)g.p2 * g.p2 * c2;
+  const long long nK1 = kk * channels * c1, nK2 = kk * c1 * c2, nWh = flat * hidden, nWd = (long long)hidden * classes;
+  g.P = nK1 + c1 + nK2 + c2 + nWh + hidden + nWd + classes;
+  if (g.P > 0x7fffffffLL) {
+    g.flat = g.oK1 = g.ob1 = g.oK2 = g.ob2 = g.oWh = g.obh = g.oWd = g.obd = 0;
+    return true;
+  }
+  g.flat = (int)flat;
+  g.oK1 = 0;
+  g.ob1 = (int)nK1;
+  g.oK2 = g.ob1 + c1;
+  g.ob2 = g.oK2 + (int)nK2;
+  g.oWh = g.ob2 + c2;
+  g.obh = g.oWh + (int)nWh;
+  g.oWd = g.obh + hidden;
+  g.obd = g.oWd + (int)nWd;
+  return true;
+}
+
+// The hidden layer's forward plan for a workgroup of T threads, from H and T alone: a pass covers
+// W = min(H, T) neighbouring columns j, and S slices (a power of two, at most 16, S W <= T) share
+// a column's sum over i, slice q taking i = q, q + S, ...
+__host__ __device__ inline int lenet_hidden_cols(int H, int T) { return H < T ? H : T; }
+__host__ __device__ inline int lenet_hidden_slices(int H, int T) {
+  const int W = lenet_hidden_cols(H, T);
+  int S = 1;
+  while (S < 16 && 2 * S * W <= T) S *= 2;
+  return S;
+}
+// LDS floats of lenet_hidden_forward's partial sums for a chunk of n samples.
+inline long long lenet_hidden_part_floats(int H, int T, int n) {
+  return (long long)lenet_hidden_slices(H, T) * n * lenet_hidden_cols(H, T);
+}
+
 // ---- phases ---------------------------------------------------------------------------------
 
 // AveragePooling2D of a window's relu(z): summed (0,0) (0,1) (1,0) (1,1) and scaled by 0.25 (exact);
@@ -450,6 +508,107 @@ __device__ __forceinline__ void lenet_conv_igrad_tiled(float* din, const float* 
     }
 }
 
+// ---- the hidden dense layer (cfa_lenet_hidden.hip) ---------------------------------------------
+
+// h[s][j] = relu(sum_i flat[s][i] Wh[i][j] + bh[j]) for a chunk of ns <= MAXN samples, Wh (F, H)
+// with j innermost (global memory or LDS): neighbouring threads take neighbouring j, so a weight
+// load is a coalesced line, and one load serves every sample of the chunk. The plan is
+// lenet_hidden_cols / lenet_hidden_slices: thread (q, j) sums i = q, q + S, ... in order from 0
+// into `part` [S][ns][W] (LDS), and the column's owner adds the slices 0 .. S - 1 in order, then
+// the bias. The order depends on (F, H, T) alone and a sample's arithmetic is its own, so the
+// chunk moves no bit. The gate is NOT stored: h > 0 exactly where z > 0, and the backward phase
+// tests the stored h again. Every thread of the workgroup calls it: it holds two barriers a pass
+// and ends on one.
+template <int MAXN>
+__device__ __forceinline__ void lenet_hidden_forward(float* __restrict__ h, const float* __restrict__ flat,
+                                                     const float* __restrict__ Wh, const float* __restrict__ bh,
+                                                     float* __restrict__ part, int ns, int F, int H, int tid, int T) {
+  const int W = lenet_hidden_cols(H, T), S = lenet_hidden_slices(H, T);
+  const int q = tid / W, jj = tid % W;
+  for (int j0 = 0; j0 < H; j0 += W) {
+    const int j = j0 + jj;
+    if (q < S && j < H) {
+      float acc[MAXN];
+#pragma unroll
+      for (int s = 0; s < MAXN; ++s) acc[s] = 0.f;
+      for (int i = q; i < F; i += S) {
+        const float w = Wh[i * H + j];
+#pragma unroll
+        for (int s = 0; s < MAXN; ++s)
+          if (s < ns) acc[s] = fmaf(flat[s * F + i], w, acc[s]);
+      }
+#pragma unroll
+      for (int s = 0; s < MAXN; ++s)
+        if (s < ns) part[(q * ns + s) * W + jj] = acc[s];
+    }
+    __syncthreads();
+    for (int idx = tid; idx < ns * W; idx += T) {
+      const int s = idx / W, c = idx % W;
+      if (j0 + c >= H) continue;
+      float z = part[s * W + c];
+      for (int r = 1; r < S; ++r) z += part[(r * ns + s) * W + c];
+      z += bh[j0 + c];
+      h[s * H + j0 + c] = z > 0.f ? z : 0.f;
+    }
+    __syncthreads();  // the next pass writes part again; the caller reads h
+  }
+}
+
+// Lanes that share one dflat sum over j: the power of two >= min(H, 64), from H alone.
+__device__ __forceinline__ int lenet_hidden_lanes(int H) {
+  int L = 1;
+  while (L < 64 && L < H) L *= 2;
+  return L;
+}
+
+// The hidden layer's backward for a chunk of ns <= MAXN samples. dh [ns][H] arrives as the output
+// dense layer's input gradient (lenet_dense_backward with F = H) and is gated in place first, by
+// the forward's own test read from the stored h (a product with 1 or 0, so a NaN upstream reaches
+// every element). Then gWh[i][j] += sum_s flat[s][i] dh[s][j] and gbh[j] += sum_s dh[s][j], one
+// thread per element (neighbouring threads neighbouring j), samples in order onto the running sum;
+// and dflat[s][i] = sum_j Wh[i][j] dh[s][j]: the L lanes of a row i (lenet_hidden_lanes) take
+// j = lane, lane + L, ... in order from 0 and fold by xor-shuffles, one weight load serving every
+// sample. Every thread of the workgroup calls it: it holds one barrier; the caller puts one after it.
+template <int MAXN>
+__device__ __forceinline__ void lenet_hidden_backward(float* __restrict__ gWh, float* __restrict__ gbh,
+                                                      float* __restrict__ dflat, float* __restrict__ dh,
+                                                      const float* __restrict__ h, const float* __restrict__ flat,
+                                                      const float* __restrict__ Wh, int ns, int F, int H, int tid,
+                                                      int T) {
+  for (int idx = tid; idx < ns * H; idx += T) dh[idx] = (h[idx] > 0.f ? 1.f : 0.f) * dh[idx];
+  __syncthreads();
+  for (int e = tid; e < F * H; e += T) {
+    const int i = e / H, j = e % H;
+    float a = gWh[e];
+    for (int s = 0; s < ns; ++s) a = fmaf(flat[s * F + i], dh[s * H + j], a);
+    gWh[e] = a;
+  }
+  for (int j = tid; j < H; j += T) {
+    float a = gbh[j];
+    for (int s = 0; s < ns; ++s) a += dh[s * H + j];
+    gbh[j] = a;
+  }
+  const int L = lenet_hidden_lanes(H);
+  for (int idx = tid; idx < F * L; idx += T) {  // T is a multiple of 64: a row's L lanes enter together
+    const int i = idx / L, lane = idx % L;
+    float acc[MAXN];
+#pragma unroll
+    for (int s = 0; s < MAXN; ++s) acc[s] = 0.f;
+    for (int j = lane; j < H; j += L) {
+      const float w = Wh[i * H + j];
+#pragma unroll
+      for (int s = 0; s < MAXN; ++s)
+        if (s < ns) acc[s] = fmaf(w, dh[s * H + j], acc[s]);
+    }
+#pragma unroll
+    for (int s = 0; s < MAXN; ++s)
+      if (s < ns) {
+        const float v = lenet_fold(acc[s], L);
+        if (lane == 0) dflat[s * F + i] = v;
+      }
+  }
+}
+
 // ---- what the average-pool and the max-pool kernels share around the phases ------------------
 
 constexpr int kLenetFinishBlock = 256;  // the workgroup of both finishing kernels
@@ -550,26 +709,26 @@ __global__ __launch_bounds__(kLenetFinishBlock) void lenet_grad_finish_kernel(Le
 // The host checks of an evaluation entry, in the order every entry of the family keeps: the
 // objective first, then CFA_E_INVALID for the arguments (ws_need: the entry's workspace bytes),
 // then CFA_E_UNSUPPORTED for classes and D. What fits LDS is the entry's own check, after these.
-inline int lenet_eval_checks(const char* fn, const void* x, const void* labels, size_t x_dev_stride,
-                             size_t label_dev_stride, int Nt, int side, int kernel, int c1, int c2, int classes,
-                             const void* models, size_t pitch, int D, int batch, int batches, double target,
-                             const void* ended, const void* cost, const void* cost_log, int log_cap,
-                             const void* epoch, const void* workspace, size_t workspace_bytes, size_t ws_need,
-                             int loss, LenetGeom& g) {
+// The entry's family gives the geometry's verdict: whether it has a model (geom_ok), its numbers
+// and rule as text for the refusal (geom_text), the model's parameters P and an image's floats.
+inline int lenet_eval_checks_for(const char* fn, const void* x, const void* labels, size_t x_dev_stride,
+                                 size_t label_dev_stride, int Nt, bool geom_ok, const char* geom_text, long long P,
+                                 long long image, int classes, const void* models, size_t pitch, int D, int batch,
+                                 int batches, double target, const void* ended, const void* cost,
+                                 const void* cost_log, int log_cap, const void* epoch, const void* workspace,
+                                 size_t workspace_bytes, size_t ws_need, int loss) {
   if (loss != CFA_LENET_LOSS_XENT && loss != CFA_LENET_LOSS_HUBER)
     return fail(CFA_E_INVALID, "%s: unknown loss kind %d (CFA_LENET_LOSS_XENT or CFA_LENET_LOSS_HUBER)", fn, loss);
   if (!x || !labels || !models || !cost || !workspace) return fail(CFA_E_INVALID, "%s: null buffer", fn);
   if (D < 1 || batch < 1 || batches < 1 || Nt < 1)
     return fail(CFA_E_INVALID, "%s: D %d, batch %d, batches %d and Nt %d must be >= 1", fn, D, batch, batches, Nt);
-  if (!lenet_geom(side, kernel, c1, c2, classes, g))
-    return fail(CFA_E_INVALID, "%s: bad geometry (side %d kernel %d c1 %d c2 %d classes %d): every dimension >= 1 "
-                "and a second pooled map of at least 1 x 1", fn, side, kernel, c1, c2, classes);
+  if (!geom_ok) return fail(CFA_E_INVALID, "%s: bad geometry %s", fn, geom_text);
   if ((long long)batch * batches > Nt)
     return fail(CFA_E_INVALID, "%s: %d batches of %d samples do not fit the %d of the test set", fn, batches, batch,
                 Nt);
-  if ((long long)pitch < g.P)
-    return fail(CFA_E_INVALID, "%s: pitch %zu below the model's %lld parameters", fn, pitch, g.P);
-  const long long set = (long long)Nt * side * side;
+  if ((long long)pitch < P)
+    return fail(CFA_E_INVALID, "%s: pitch %zu below the model's %lld parameters", fn, pitch, P);
+  const long long set = (long long)Nt * image;
   if ((x_dev_stride != 0 && (long long)x_dev_stride < set) || (label_dev_stride != 0 && (long long)label_dev_stride < Nt))
     return fail(CFA_E_INVALID, "%s: device strides %zu / %zu below one device's set (%lld / %d)", fn, x_dev_stride,
                 label_dev_stride, set, Nt);
@@ -584,34 +743,64 @@ inline int lenet_eval_checks(const char* fn, const void* x, const void* labels, 
   return CFA_OK;
 }
 
+// The five-number family's verdict text.
+inline void lenet_geom_text(char (&text)[192], int side, int kernel, int c1, int c2, int classes) {
+  snprintf(text, sizeof text, "(side %d kernel %d c1 %d c2 %d classes %d): every dimension >= 1 and a second pooled "
+           "map of at least 1 x 1", side, kernel, c1, c2, classes);
+}
+
+inline int lenet_eval_checks(const char* fn, const void* x, const void* labels, size_t x_dev_stride,
+                             size_t label_dev_stride, int Nt, int side, int kernel, int c1, int c2, int classes,
+                             const void* models, size_t pitch, int D, int batch, int batches, double target,
+                             const void* ended, const void* cost, const void* cost_log, int log_cap,
+                             const void* epoch, const void* workspace, size_t workspace_bytes, size_t ws_need,
+                             int loss, LenetGeom& g) {
+  char text[192];
+  lenet_geom_text(text, side, kernel, c1, c2, classes);
+  const bool ok = lenet_geom(side, kernel, c1, c2, classes, g);
+  return lenet_eval_checks_for(fn, x, labels, x_dev_stride, label_dev_stride, Nt, ok, text, ok ? g.P : 0,
+                               (long long)side * side, classes, models, pitch, D, batch, batches, target, ended, cost,
+                               cost_log, log_cap, epoch, workspace, workspace_bytes, ws_need, loss);
+}
+
 // The same for a gradient entry. Its workspace is checked by the entry after what fits LDS, as
 // cfa_lenet_grad_loss_f32 always has.
-inline int lenet_grad_checks(const char* fn, const void* x, const void* labels, size_t x_dev_stride,
-                             size_t label_dev_stride, int Nt, int side, int kernel, int c1, int c2, int classes,
-                             const void* models, size_t pitch, int D, int batch, const void* grads, size_t gpitch,
-                             const void* workspace, int loss_kind, LenetGeom& g) {
+inline int lenet_grad_checks_for(const char* fn, const void* x, const void* labels, size_t x_dev_stride,
+                                 size_t label_dev_stride, int Nt, bool geom_ok, const char* geom_text, long long P,
+                                 long long image, int classes, const void* models, size_t pitch, int D, int batch,
+                                 const void* grads, size_t gpitch, const void* workspace, int loss_kind) {
   if (loss_kind != CFA_LENET_LOSS_XENT && loss_kind != CFA_LENET_LOSS_HUBER)
     return fail(CFA_E_INVALID, "%s: unknown loss kind %d (CFA_LENET_LOSS_XENT or CFA_LENET_LOSS_HUBER)", fn,
                 loss_kind);
   if (!x || !labels || !models || !grads || !workspace) return fail(CFA_E_INVALID, "%s: null buffer", fn);
   if (D < 1 || batch < 1 || Nt < 1)
     return fail(CFA_E_INVALID, "%s: D %d, batch %d and Nt %d must be >= 1", fn, D, batch, Nt);
-  if (!lenet_geom(side, kernel, c1, c2, classes, g))
-    return fail(CFA_E_INVALID, "%s: bad geometry (side %d kernel %d c1 %d c2 %d classes %d): every dimension >= 1 "
-                "and a second pooled map of at least 1 x 1", fn, side, kernel, c1, c2, classes);
+  if (!geom_ok) return fail(CFA_E_INVALID, "%s: bad geometry %s", fn, geom_text);
   if (batch > Nt)
     return fail(CFA_E_INVALID, "%s: a batch of %d samples does not fit the %d of the training set", fn, batch, Nt);
-  if ((long long)pitch < g.P)
-    return fail(CFA_E_INVALID, "%s: pitch %zu below the model's %lld parameters", fn, pitch, g.P);
-  if ((long long)gpitch < g.P)
-    return fail(CFA_E_INVALID, "%s: gpitch %zu below the model's %lld parameters", fn, gpitch, g.P);
-  const long long set = (long long)Nt * side * side;
+  if ((long long)pitch < P)
+    return fail(CFA_E_INVALID, "%s: pitch %zu below the model's %lld parameters", fn, pitch, P);
+  if ((long long)gpitch < P)
+    return fail(CFA_E_INVALID, "%s: gpitch %zu below the model's %lld parameters", fn, gpitch, P);
+  const long long set = (long long)Nt * image;
   if ((x_dev_stride != 0 && (long long)x_dev_stride < set) || (label_dev_stride != 0 && (long long)label_dev_stride < Nt))
     return fail(CFA_E_INVALID, "%s: device strides %zu / %zu below one device's set (%lld / %d)", fn, x_dev_stride,
                 label_dev_stride, set, Nt);
   if (classes > 64) return fail(CFA_E_UNSUPPORTED, "%s: more than 64 classes", fn);
   if (D > 65535) return fail(CFA_E_UNSUPPORTED, "%s: more than 65535 devices", fn);
   return CFA_OK;
+}
+
+inline int lenet_grad_checks(const char* fn, const void* x, const void* labels, size_t x_dev_stride,
+                             size_t label_dev_stride, int Nt, int side, int kernel, int c1, int c2, int classes,
+                             const void* models, size_t pitch, int D, int batch, const void* grads, size_t gpitch,
+                             const void* workspace, int loss_kind, LenetGeom& g) {
+  char text[192];
+  lenet_geom_text(text, side, kernel, c1, c2, classes);
+  const bool ok = lenet_geom(side, kernel, c1, c2, classes, g);
+  return lenet_grad_checks_for(fn, x, labels, x_dev_stride, label_dev_stride, Nt, ok, text, ok ? g.P : 0,
+                               (long long)side * side, classes, models, pitch, D, batch, grads, gpitch, workspace,
+                               loss_kind);
 }
 
 }  // namespace

@@ -556,12 +556,41 @@ class Engine:
     # -- validation pass of a TF2 LeNet-1 population ------------------------------------------
     def lenet_params(self, geom: Sequence[int]) -> int:
         """Parameters of a LeNet-family model (cfa_lenet_params); 0 for a geometry without one."""
-        return int(_lib.load().cfa_lenet_params(*(int(v) for v in geom)))
+        geom = tuple(int(v) for v in geom)
+        if len(geom) == 7:
+            return int(_lib.load().cfa_lenet_hidden_params(*geom))
+        return int(_lib.load().cfa_lenet_params(*geom))
 
-    def lenet_workspace(self, D: int, batches: int, pool: str = "avg") -> torch.Tensor:
-        """Workspace of the batch losses (cfa_lenet_eval_workspace_bytes, or cfa_lenet_max_eval_workspace_bytes
-        for ``pool="max"``)."""
-        fn = getattr(_lib.load(), f"cfa_lenet_{_lib.lenet_pool(pool)}eval_workspace_bytes")
+    @staticmethod
+    def _lenet_sets(geom: Sequence[int], pool: str, x: torch.Tensor, labels: torch.Tensor,
+                    models: torch.Tensor) -> tuple:
+        """What lenet_eval and lenet_grad take from their geometry, set and models: (geom, entry-point
+        infix, D, P, Nt, x_stride, label_stride), with the set shared ([Nt, image]: strides 0) or one
+        per device ([D, Nt, image]); image is [side, side], or [side, side, channels] for seven numbers."""
+        geom, infix, image = _lib.lenet_family(geom, pool)
+        D, P = _check_nd(models, "models", pitched=True)
+        nd = 1 + len(image)  # 3, or 4 with the channel axis of the hidden-layer family
+        if x.dim() == nd:
+            Nt = _check_nd(x, "x", nd)[0]
+            x_stride = label_stride = 0
+            shapes = ((Nt,) + image, (Nt,))
+        else:
+            what = "[Nt, side, side] or [D, Nt, side, side]" if nd == 3 else \
+                "[Nt, side, side, channels] or [D, Nt, side, side, channels]"
+            Nt = _check_nd(x, "x", nd + 1, what=what)[1]
+            x_stride, label_stride = Nt * int(np.prod(image)), Nt
+            shapes = ((D, Nt) + image, (D, Nt))
+        _check_tables(("labels", labels, torch.int32))
+        if (tuple(x.shape), tuple(labels.shape)) != shapes:
+            raise ValueError(f"x and labels must be {shapes[0]} and {shapes[1]} for these models and this geometry")
+        return geom, infix, D, P, Nt, x_stride, label_stride
+
+    def lenet_workspace(self, D: int, batches: int, pool: str = "avg",
+                        geom: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """Workspace of the batch losses (cfa_lenet_eval_workspace_bytes, cfa_lenet_max_eval_workspace_bytes
+        for ``pool="max"``, or cfa_lenet_hidden_eval_workspace_bytes for a seven-number ``geom``)."""
+        infix = _lib.lenet_pool(pool) if geom is None else _lib.lenet_family(geom, pool)[1]
+        fn = getattr(_lib.load(), f"cfa_lenet_{infix}eval_workspace_bytes")
         n = int(fn(int(D), int(batches)))
         return torch.empty(max(n // 4, 1), dtype=torch.float32, device=self.device)
 
@@ -584,24 +613,13 @@ class Engine:
         softmax(z)[label])); ValueError for any other, before any device call. ``pool``: "avg"
         (LeNet-1's AveragePooling2D) or "max" (cfa_lenet_max_eval_loss_f32: the drivers' max-pool
         CNNs, ``workspace`` from ``lenet_workspace(D, batches, "max")``); ValueError for any
-        other. The library validates the rest (CFAError)."""
-        kind, infix = _lib.lenet_loss_kind(loss), _lib.lenet_pool(pool)
-        geom = tuple(int(v) for v in geom)
-        if len(geom) != 5:
-            raise ValueError("geom must be (side, kernel, c1, c2, classes)")
-        side = geom[0]
-        D, P = _check_nd(models, "models", pitched=True)
-        if x.dim() == 3:
-            Nt = _check_nd(x, "x", 3)[0]
-            x_stride = label_stride = 0
-            shapes = ((Nt, side, side), (Nt,))
-        else:
-            Nt = _check_nd(x, "x", 4, what="[Nt, side, side] or [D, Nt, side, side]")[1]
-            x_stride, label_stride = Nt * side * side, Nt
-            shapes = ((D, Nt, side, side), (D, Nt))
-        _check_tables(("labels", labels, torch.int32))
-        if (tuple(x.shape), tuple(labels.shape)) != shapes:
-            raise ValueError(f"x and labels must be {shapes[0]} and {shapes[1]} for these models and this geometry")
+        other. A ``geom`` of seven numbers (side, channels, kernel, c1, c2, hidden, classes) is the
+        hidden-layer family (cfa_lenet_hidden_eval_loss_f32: the CIFAR drivers' ``CIFAR_LENET``):
+        ``x`` is [Nt, side, side, channels] or [D, Nt, side, side, channels], always with the
+        channel axis, ``workspace`` from ``lenet_workspace(D, batches, geom=geom)``, and
+        ``pool="max"`` a ValueError. The library validates the rest (CFAError)."""
+        kind = _lib.lenet_loss_kind(loss)
+        geom, infix, D, P, Nt, x_stride, label_stride = self._lenet_sets(geom, pool, x, labels, models)
         if P != self.lenet_params(geom):
             raise ValueError("models' row size does not match the geometry")
         batch, batches = int(batch), int(batches)
@@ -637,8 +655,9 @@ class Engine:
     def lenet_grad_workspace(self, D: int, batch: int, geom: Sequence[int], pool: str = "avg") -> torch.Tensor:
         """Workspace of the sample groups' partial gradients (cfa_lenet_grad_workspace_bytes, or
         cfa_lenet_max_grad_workspace_bytes for ``pool="max"``)."""
-        fn = getattr(_lib.load(), f"cfa_lenet_{_lib.lenet_pool(pool)}grad_workspace_bytes")
-        n = int(fn(int(D), int(batch), *(int(v) for v in geom)))
+        geom, infix, _ = _lib.lenet_family(geom, pool)
+        fn = getattr(_lib.load(), f"cfa_lenet_{infix}grad_workspace_bytes")
+        n = int(fn(int(D), int(batch), *geom))
         return torch.empty(max(n // 4, 1), dtype=torch.float32, device=self.device)
 
     def lenet_grad(self, geom: Sequence[int], x: torch.Tensor, labels: torch.Tensor, models: torch.Tensor,
@@ -660,25 +679,12 @@ class Engine:
         "xent" or "huber" as ``lenet_eval``'s ``loss`` (here ``loss`` is the output buffer);
         ValueError for any other, before any device call. ``pool``: "avg" or "max" as
         ``lenet_eval``'s (cfa_lenet_max_grad_loss_f32, ``workspace`` from
-        ``lenet_grad_workspace(D, batch, geom, "max")``). The library validates the rest
-        (CFAError)."""
-        kind, infix = _lib.lenet_loss_kind(loss_kind), _lib.lenet_pool(pool)
-        geom = tuple(int(v) for v in geom)
-        if len(geom) != 5:
-            raise ValueError("geom must be (side, kernel, c1, c2, classes)")
-        side = geom[0]
-        D, P = _check_nd(models, "models", pitched=True)
-        if x.dim() == 3:
-            Nt = _check_nd(x, "x", 3)[0]
-            x_stride = label_stride = 0
-            shapes = ((Nt, side, side), (Nt,))
-        else:
-            Nt = _check_nd(x, "x", 4, what="[Nt, side, side] or [D, Nt, side, side]")[1]
-            x_stride, label_stride = Nt * side * side, Nt
-            shapes = ((D, Nt, side, side), (D, Nt))
-        _check_tables(("labels", labels, torch.int32))
-        if (tuple(x.shape), tuple(labels.shape)) != shapes:
-            raise ValueError(f"x and labels must be {shapes[0]} and {shapes[1]} for these models and this geometry")
+        ``lenet_grad_workspace(D, batch, geom, "max")``). A ``geom`` of seven numbers is the
+        hidden-layer family as in ``lenet_eval`` (cfa_lenet_hidden_grad_loss_f32), with ``x``
+        [Nt, side, side, channels] or [D, Nt, side, side, channels]. The library validates the
+        rest (CFAError)."""
+        kind = _lib.lenet_loss_kind(loss_kind)
+        geom, infix, D, P, Nt, x_stride, label_stride = self._lenet_sets(geom, pool, x, labels, models)
         if P != self.lenet_params(geom):
             raise ValueError("models' row size does not match the geometry")
         batch = int(batch)

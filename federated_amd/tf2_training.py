@@ -11,7 +11,9 @@ train on ``keras.losses.Huber()`` between the label and the true class's probabi
 training set, the batch size, each device's position in its set, the gradient and loss buffers)
 and computes all D gradients in one ``cfa_lenet_grad_loss_f32`` call, for the model family, geometry and
 row layout of ``tf2_validation`` (``lenet_layer_shapes``); ``pool="max"`` serves the drivers'
-max-pool CNNs (``MNIST_CNN32``, ``MNIST_CNN14``) through ``cfa_lenet_max_grad_loss_f32``. With ``PopulationOptimizer`` and
+max-pool CNNs (``MNIST_CNN32``, ``MNIST_CNN14``) through ``cfa_lenet_max_grad_loss_f32``, and a
+geometry of seven numbers the CIFAR drivers' hidden-layer LeNet (``CIFAR_LENET``, images
+``[side, side, channels]``) through ``cfa_lenet_hidden_grad_loss_f32``. With ``PopulationOptimizer`` and
 ``LenetValidation`` one epoch of a population stays on the device::
 
     val.validate(pop.models, skip=pop.ended, ended=pop.ended)
@@ -30,9 +32,11 @@ import torch
 
 from ._lib import lenet_loss_kind, lenet_pool
 
-from .tf2_validation import LENET1, MAX_CLASSES, MNIST_CNN14, MNIST_CNN32, _stages, lenet_layer_shapes, lenet_size
+from .tf2_validation import (CIFAR_LENET, LENET1, MAX_CLASSES, MNIST_CNN14, MNIST_CNN32, _family, _stages,
+                             lenet_layer_shapes, lenet_size)
 
-__all__ = ["LenetTraining", "lenet_size", "lenet_layer_shapes", "LENET1", "MNIST_CNN32", "MNIST_CNN14"]
+__all__ = ["LenetTraining", "lenet_size", "lenet_layer_shapes", "LENET1", "MNIST_CNN32", "MNIST_CNN14",
+           "CIFAR_LENET"]
 
 
 class LenetTraining:
@@ -50,17 +54,22 @@ class LenetTraining:
         device in [0, D). ValueError for a geometry without a model (p2 < 1) or with more than
         64 classes, mismatched shapes, ``batch`` below 1 or above Nt, a label or a ``src`` out of
         range, a ``D`` that disagrees with a per-device set, a ``loss`` other than "xent" or
-        "huber" (the plan is the same for both) and a ``pool`` other than "avg" or "max"."""
+        "huber" (the plan is the same for both) and a ``pool`` other than "avg" or "max". A
+        ``geom`` of seven numbers (``CIFAR_LENET``) takes ``x_shape`` [Nt, side, side, channels] or
+        [D, Nt, side, side, channels]; ``hidden < 1``, a missing channel axis and ``pool="max"``
+        are ValueErrors."""
         lenet_loss_kind(loss)
         lenet_pool(pool)
-        side, k, c1, c2, classes, _ = _stages(geom)
+        classes = _stages(geom)[4]
+        geom, image, text = _family(geom, pool)
         if classes > MAX_CLASSES:
             raise ValueError(f"more than {MAX_CLASSES} classes")
         xs, ls = tuple(int(v) for v in x_shape), tuple(int(v) for v in labels_shape)
-        if len(xs) not in (3, 4) or xs[-2:] != (side, side) or ls != xs[:-2] or min(xs) < 1:
-            raise ValueError(f"x must be [Nt, {side}, {side}] with labels [Nt], or [D, Nt, {side}, {side}] with "
+        n = len(image)
+        if len(xs) not in (n + 1, n + 2) or xs[-n:] != image or ls != xs[:-n] or min(xs) < 1:
+            raise ValueError(f"x must be [Nt, {text}] with labels [Nt], or [D, Nt, {text}] with "
                              f"labels [D, Nt]; got {xs} and {ls}")
-        Nt, per_device = xs[-3], xs[0] if len(xs) == 4 else 0
+        Nt, per_device = xs[-n - 1], xs[0] if len(xs) == n + 2 else 0
         batch = int(batch)
         if batch < 1 or batch > Nt:
             raise ValueError(f"a batch of {batch} samples does not fit the {Nt} of the training set")
@@ -81,7 +90,7 @@ class LenetTraining:
                 raise ValueError(f"src must hold one integer per device ({n})")
             if s.min() < 0 or s.max() >= n:
                 raise ValueError(f"src must lie in [0, {n})")
-        return {"geom": (side, k, c1, c2, classes), "P": lenet_size(geom), "Nt": Nt, "batch": batch,
+        return {"geom": geom, "P": lenet_size(geom), "Nt": Nt, "batch": batch,
                 "per_device": per_device}
 
     def __init__(self, engine, geom: Sequence[int], x_train: torch.Tensor, labels: torch.Tensor, batch: int,
@@ -94,7 +103,8 @@ class LenetTraining:
         ``federated_learning_keras_consensus_FL_MNIST.py:369-377``: ``keras.losses.Huber()``
         between the integer label itself and the softmax probability of the true class); it is
         kept as ``loss_kind`` (``loss`` is the buffer of the batch losses). ``pool``: "avg"
-        (LeNet-1) or "max" (``MNIST_CNN32``, ``MNIST_CNN14``)."""
+        (LeNet-1) or "max" (``MNIST_CNN32``, ``MNIST_CNN14``). With a geometry of seven numbers
+        (``CIFAR_LENET``) ``x_train`` is [Nt, side, side, channels] or [D, Nt, side, side, channels]."""
         info = self.check(geom, x_train.shape, labels.shape, batch, loss=loss, pool=pool)
         self.engine, self.geom, self.P, self.loss_kind, self.pool = engine, info["geom"], info["P"], loss, pool
         self.x_train, self.labels = x_train, labels
@@ -102,8 +112,8 @@ class LenetTraining:
         if labels.dtype != torch.int32 or not labels.is_cuda:
             raise TypeError("labels must be an int32 CUDA tensor")
         lo, hi = int(labels.min().item()), int(labels.max().item())
-        if lo < 0 or hi >= self.geom[4]:
-            raise ValueError(f"labels must lie in [0, {self.geom[4]})")
+        if lo < 0 or hi >= self.geom[-1]:
+            raise ValueError(f"labels must lie in [0, {self.geom[-1]})")
         self.D = 0  # set by allocate(), or by the first gradients()
         self.grads = self.loss = self.cursor = self.workspace = None
 

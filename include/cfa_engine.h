@@ -838,6 +838,72 @@ CFA_API int cfa_lenet_max_grad_loss_f32(const float* x, size_t x_dev_stride, con
                                         float* grads, size_t gpitch, float* loss,
                                         void* workspace, size_t workspace_bytes, int loss_kind, void* stream);
 
+/* (TF2 drivers) The same two passes for the CIFAR drivers' HIDDEN-LAYER LeNet, -modelselection 1 of
+ * federated_learning_keras_consensus_FL_threads_CIFAR_crossentropy.py:179-186 and of
+ * ..._CIFAR_crossentropy_gradients_exchange.py (elif condition == 1), a family of SEVEN numbers
+ * (side, channels, kernel, c1, c2, hidden, classes):
+ *   x [side, side, channels] -> Conv2D(c1, kernel x kernel, valid, relu) -> AveragePooling2D(2 x 2)
+ *     -> Conv2D(c2, kernel x kernel, valid, relu) -> AveragePooling2D(2 x 2) -> Flatten (NHWC)
+ *     -> Dense(hidden, relu) -> Dense(classes, softmax)
+ * with (32, 3, 5, 4, 8, 128, 10) for the drivers: 32 -> 28 -> 14 -> 10 -> 5, flat = 200 and
+ * P = 304 + 808 + 25728 + 1290 = 28130 (cfa_lenet_hidden_params; 0 for a geometry without a model:
+ * a dimension below 1, hidden included, or a second pooled map below 1 x 1).
+ *   x       [Nt, side, side, channels] fp32, NHWC, shared (x_dev_stride 0), or one set per device
+ *           x_dev_stride >= Nt * side * side * channels floats apart.
+ *   models  [D, pitch]: a row is get_weights() order, C-order, eight tensors:
+ *           K1 (k, k, channels, c1), b1, K2 (k, k, c1, c2), b2, Wh (flat, hidden), bh,
+ *           Wd (hidden, classes), bd, with flat = p2 * p2 * c2 and Flatten index (y * p2 + x) * c2 + c.
+ * The convolutions, the average pool (an odd last row and column dropped; backward 0.25 d(pooled)
+ * to each kept position), the z > 0 relu gates, both objectives, the log-softmax form, NaN for a
+ * label outside [0, classes) and every other argument are those of cfa_lenet_eval_loss_f32 /
+ * cfa_lenet_grad_loss_f32. What is new:
+ *   forward:  h[j] = relu(sum_i flat[i] Wh[i][j] + bh[j]); z = h Wd + bd.
+ *   backward: dh[j] = (sum_c Wd[j][c] dz[c]) where the forward's own h[j] > 0 (TF's ReluGrad; the
+ *             gate is not stored, h > 0 exactly where its pre-activation was; applied as a product
+ *             with 1 or 0, so a NaN upstream reaches the whole row), dWh = flat (x) dh, dbh = dh,
+ *             dflat[i] = sum_j Wh[i][j] dh[j].
+ * The model is NOT held in LDS (the plan of the max-pool entries): weights are read from global
+ * memory with the output index innermost, LDS holds a chunk's activations, their gradients, the
+ * pools' gate bytes and the hidden layer's partial sums. fp32, explicit fma, no matrix instructions.
+ * Deterministic, no atomics: every sum has a fixed order that depends on the geometry alone (a
+ * hidden sum is cut into at most 16 interleaved slices from hidden and the workgroup size, added
+ * in order; the gradient kernel adds samples in order within groups of 8 and the groups in
+ * order), so a device's cost, loss and gradient row have the same bits alone or in a population,
+ * whatever D, skip, src, first or the GPU's CU count and LDS are, and the loss of the gradient
+ * call is bit for bit the batch loss of the validation call on the same samples. No host read,
+ * allocation or attribute call after cfa_device_prepare: capture-safe. Two launches per call.
+ * Accuracy is that of fp32 sums in this order: about 1e-6 normwise per tensor of the fp64 value on
+ * well-conditioned tensors; a bias gradient whose terms of both signs cancel to a thousandth of
+ * their size keeps about 5e-5 (measured), as any fp32 sum of them would.
+ * workspace: at least cfa_lenet_hidden_eval_workspace_bytes(D, batches) or
+ * cfa_lenet_hidden_grad_workspace_bytes(D, batch, geometry) bytes of DEVICE memory
+ * (D * ceil(batch / 8) * (P + 8) floats; 0 for D, batch(es) < 1 or a geometry without a model).
+ * Errors, in the siblings' order: CFA_E_INVALID for an unknown loss (checked first, before any
+ * buffer), then for a null buffer, D, batch, batches or Nt < 1, a bad geometry, batch*batches > Nt
+ * (batch > Nt), pitch or gpitch < P, a short device stride, only one of cost_log / epoch, a
+ * workspace too small, a non-finite target with ended; CFA_E_UNSUPPORTED for classes > 64,
+ * D > 65535, and only then for ONE sample's state beyond a workgroup's LDS (validation: image,
+ * two pooled maps, h, logits, the partial sums and the batch's losses; gradient: those, their
+ * gradients and the gated map of stage 2; the gradient entry checks its workspace after this). */
+CFA_API size_t cfa_lenet_hidden_params(int side, int channels, int kernel, int c1, int c2, int hidden, int classes);
+CFA_API size_t cfa_lenet_hidden_eval_workspace_bytes(int D, int batches);
+CFA_API int cfa_lenet_hidden_eval_loss_f32(const float* x, size_t x_dev_stride, const int32_t* labels,
+                                           size_t label_dev_stride, int Nt, int side, int channels, int kernel,
+                                           int c1, int c2, int hidden, int classes, const float* models,
+                                           size_t pitch, int D, int batch, int batches, const int32_t* skip,
+                                           double target, int32_t* ended, double* cost, double* cost_log,
+                                           int log_cap, unsigned long long* epoch, void* workspace,
+                                           size_t workspace_bytes, int loss, void* stream);
+CFA_API size_t cfa_lenet_hidden_grad_workspace_bytes(int D, int batch, int side, int channels, int kernel, int c1,
+                                                     int c2, int hidden, int classes);
+CFA_API int cfa_lenet_hidden_grad_loss_f32(const float* x, size_t x_dev_stride, const int32_t* labels,
+                                           size_t label_dev_stride, int Nt, int side, int channels, int kernel,
+                                           int c1, int c2, int hidden, int classes, const float* models,
+                                           size_t pitch, int D, const int32_t* src, const long long* first,
+                                           int batch, const int32_t* skip, float* grads, size_t gpitch,
+                                           float* loss, void* workspace, size_t workspace_bytes, int loss_kind,
+                                           void* stream);
+
 /* (a1-a6 batched) Population round: one launch mixes D devices.
  * For device d, CSR entries e in [csr_ptr[d], csr_ptr[d+1]) list its sources in order; the
  * FIRST entry is the device's own (local) bucket. Source e is src_ptrs[csr_idx[e]], output d
