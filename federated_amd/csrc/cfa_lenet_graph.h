@@ -46,74 +46,38 @@ namespace {
 
 // ---- geometry (host) ----------------------------------------------------------------------
 
+// One geometry for every kernel of the family. With an input of `cin` channels and a hidden dense
+// layer (cfa_lenet_hidden.hip: the CIFAR drivers' -modelselection 1) the graph is
+//   x [side, side, cin] -> Conv2D(c1) -> relu -> pool -> Conv2D(c2) -> relu -> pool
+//     -> Flatten -> Dense(H, relu) -> Dense(classes)
+// and a model row K1 (k, k, cin, c1) b1 K2 (k, k, c1, c2) b2 Wh (flat, H) bh Wd (H, classes) bd.
+// Without a hidden layer H = 0, Wh and bh are empty (oWh = obh = oWd) and Wd is (flat, classes).
 struct LenetGeom {
-  int side, k, c1, c2, C;
+  int side, cin, k, c1, c2, H, C;
   int s1, p1, s2, p2;  // conv / pool output sides of the two stages
   int flat;            // p2 * p2 * c2
-  int oK1, ob1, oK2, ob2, oWd, obd;  // offsets of the six tensors in a model row
+  int oK1, ob1, oK2, ob2, oWh, obh, oWd, obd;  // offsets of the tensors in a model row
   long long P;
 };
 
-// The family's geometry from the caller's five numbers; false for a geometry that has no model
-// (a dimension < 1, a kernel larger than its input, an empty pooled map). Offsets are valid only
-// while P fits an int; a kernel's entry refuses a model that large before any launch.
-inline bool lenet_geom(int side, int kernel, int c1, int c2, int classes, LenetGeom& g) {
-  if (side < 1 || kernel < 1 || c1 < 1 || c2 < 1 || classes < 1) return false;
-  g.side = side, g.k = kernel, g.c1 = c1, g.c2 = c2, g.C = classes;
+// The geometry from the caller's seven numbers; with_hidden: whether the family has a hidden layer
+// (`hidden` counts only then). false for a geometry that has no model: a dimension < 1 (hidden
+// included where there is one), a kernel larger than its input, an empty pooled map. Offsets are
+// valid only while P fits an int; a kernel's entry refuses a model that large before any launch.
+inline bool lenet_geom(int side, int channels, int kernel, int c1, int c2, int hidden, int classes, bool with_hidden,
+                       LenetGeom& g) {
+  if (side < 1 || channels < 1 || kernel < 1 || c1 < 1 || c2 < 1 || (with_hidden && hidden < 1) || classes < 1)
+    return false;
+  g.side = side, g.cin = channels, g.k = kernel, g.c1 = c1, g.c2 = c2, g.H = with_hidden ? hidden : 0, g.C = classes;
   g.s1 = side - kernel + 1;
   g.p1 = g.s1 > 0 ? g.s1 / 2 : 0;
   g.s2 = g.p1 - kernel + 1;
   g.p2 = g.s2 > 0 ? g.s2 / 2 : 0;
   if (g.p2 < 1) return false;
   const long long kk = (long long)kernel * kernel, flat = (long long)g.p2 * g.p2 * c2;
-  const long long nK1 = kk * c1, nK2 = kk * c1 * c2, nWd = flat * classes;
-  g.P = nK1 + c1 + nK2 + c2 + nWd + classes;
-  if (g.P > 0x7fffffffLL) {
-    g.flat = g.oK1 = g.ob1 = g.oK2 = g.ob2 = g.oWd = g.obd = 0;
-    return true;
-  }
-  g.flat = (int)flat;
-  g.oK1 = 0;
-  g.ob1 = (int)nK1;
-  g.oK2 = g.ob1 + c1;
-  g.ob2 = g.oK2 + (int)nK2;
-  g.oWd = g.ob2 + c2;
-  g.obd = g.oWd + (int)nWd;
-  return true;
-}
-
-// LDS floats one sample's forward pass needs: the image, the two pooled maps and the logits.
-inline long long lenet_sample_floats(const LenetGeom& g) {
-  return (long long)g.side * g.side + (long long)g.p1 * g.p1 * g.c1 + g.flat + g.C;
-}
-
-// The family with an input of `cin` channels and a hidden dense layer (cfa_lenet_hidden.hip: the
-// CIFAR drivers' -modelselection 1), from the caller's seven numbers:
-//   x [side, side, cin] -> Conv2D(c1) -> relu -> AveragePooling2D -> Conv2D(c2) -> relu -> AveragePooling2D
-//     -> Flatten -> Dense(H, relu) -> Dense(classes)
-// A model row is K1 (k, k, cin, c1) b1 K2 (k, k, c1, c2) b2 Wh (flat, H) bh Wd (H, classes) bd.
-struct LenetHiddenGeom {
-  int side, cin, k, c1, c2, H, C;
-  int s1, p1, s2, p2;
-  int flat;
-  int oK1, ob1, oK2, ob2, oWh, obh, oWd, obd;
-  long long P;
-};
-
-// false for a geometry that has no model: a dimension < 1 (hidden included), a kernel larger than
-// its input, an empty pooled map. Offsets are valid only while P fits an int, as lenet_geom's.
-inline bool lenet_hidden_geom(int side, int channels, int kernel, int c1, int c2, int hidden, int classes,
-                              LenetHiddenGeom& g) {
-  if (side < 1 || channels < 1 || kernel < 1 || c1 < 1 || c2 < 1 || hidden < 1 || classes < 1) return false;
-  g.side = side, g.cin = channels, g.k = kernel, g.c1 = c1, g.c2 = c2, g.H = hidden, g.C = classes;
-  g.s1 = side - kernel + 1;
-  g.p1 = g.s1 > 0 ? g.s1 / 2 : 0;
-  g.s2 = g.p1 - kernel + 1;
-  g.p2 = g.s2 > 0 ? g.s2 / 2 : 0;
-  if (g.p2 < 1) return false;
-  const long long kk = (long long)kernel * kernel, flat = (long long)g.p2 * g.p2 * c2;
-  const long long nK1 = kk * channels * c1, nK2 = kk * c1 * c2, nWh = flat * hidden, nWd = (long long)hidden * classes;
-  g.P = nK1 + c1 + nK2 + c2 + nWh + hidden + nWd + classes;
+  const long long nK1 = kk * channels * c1, nK2 = kk * c1 * c2, nWh = flat * g.H;
+  const long long nWd = (with_hidden ? (long long)g.H : flat) * classes;
+  g.P = nK1 + c1 + nK2 + c2 + nWh + g.H + nWd + classes;
   if (g.P > 0x7fffffffLL) {
     g.flat = g.oK1 = g.ob1 = g.oK2 = g.ob2 = g.oWh = g.obh = g.oWd = g.obd = 0;
     return true;
@@ -125,9 +89,19 @@ inline bool lenet_hidden_geom(int side, int channels, int kernel, int c1, int c2
   g.ob2 = g.oK2 + (int)nK2;
   g.oWh = g.ob2 + c2;
   g.obh = g.oWh + (int)nWh;
-  g.oWd = g.obh + hidden;
+  g.oWd = g.obh + g.H;
   g.obd = g.oWd + (int)nWd;
   return true;
+}
+
+// The five-number spelling: one channel, no hidden layer.
+inline bool lenet_geom(int side, int kernel, int c1, int c2, int classes, LenetGeom& g) {
+  return lenet_geom(side, 1, kernel, c1, c2, 0, classes, false, g);
+}
+
+// LDS floats one sample's forward pass needs: the image, the two pooled maps, h and the logits.
+inline long long lenet_sample_floats(const LenetGeom& g) {
+  return (long long)g.side * g.side * g.cin + (long long)g.p1 * g.p1 * g.c1 + g.flat + g.H + g.C;
 }
 
 // The hidden layer's forward plan for a workgroup of T threads, from H and T alone: a pass covers
@@ -613,9 +587,9 @@ __device__ __forceinline__ void lenet_hidden_backward(float* __restrict__ gWh, f
 
 constexpr int kLenetFinishBlock = 256;  // the workgroup of both finishing kernels
 
-// The arguments of an evaluation kernel (cfa_lenet.hip, cfa_lenet_max.hip).
+// The arguments of an evaluation kernel (cfa_lenet.hip, cfa_lenet_global.h).
 struct LenetArgs {
-  const float* x;         // [Nt][side][side], or [D][Nt][side][side] with x_stride
+  const float* x;         // [Nt][side][side][cin], or [D][Nt][side][side][cin] with x_stride
   const int32_t* labels;  // [Nt], or [D][Nt] with label_stride
   long long x_stride, label_stride;
   const float* models;    // [D][pitch]
@@ -664,9 +638,9 @@ __global__ __launch_bounds__(kLenetFinishBlock) void lenet_finish_kernel(LenetFi
   }
 }
 
-// The arguments of a gradient kernel (cfa_lenet_grad.hip, cfa_lenet_max.hip).
+// The arguments of a gradient kernel (cfa_lenet_grad.hip, cfa_lenet_global.h).
 struct LenetGradArgs {
-  const float* x;         // [Nt][side][side], or [D][Nt][side][side] with x_stride
+  const float* x;         // [Nt][side][side][cin], or [D][Nt][side][side][cin] with x_stride
   const int32_t* labels;  // [Nt], or [D][Nt] with label_stride
   long long x_stride, label_stride;
   const float* models;    // [D][pitch]

@@ -3,217 +3,35 @@
 // (federated_learning_keras_consensus_FL_threads_MNIST_crossentropy_gradients_exchange.py:170-182,
 // conditions 1 and 2: Conv2D(32 or 14, 3 x 3, relu) -> MaxPooling2D -> Conv2D(64, 3 x 3, relu) ->
 // MaxPooling2D -> Flatten -> Dense(10, softmax); used at :321-337, :360-385 and :430-455), on the
-// phases of cfa_lenet_graph.h with LenetMaxPool / LenetMaxGated in the pool's place. Geometry, row
-// layout, objectives, argument checks and both finishing kernels are the average-pool family's.
+// plan of cfa_lenet_global.h with LenetMaxPool / LenetMaxGated in the pool's place. Geometry (five
+// numbers, one input channel), row layout, objectives, argument checks and both finishing kernels
+// are the average-pool family's.
 //
-// The plan keeps the MODEL OUT OF LDS (34 826 parameters are 136 KiB): a workgroup reads its
-// device's weights from global memory, where a [D, P] stack of these models stays in L2 / the
-// Infinity Cache, with co innermost, so a wave's weight load is one coalesced line that serves the
-// window's four positions (and, at k = 3, the 4 x 4 inputs under a window are read once for all 9
-// taps). LDS holds a chunk's activations, their gradients, the pool decisions (a byte per pooled
-// element) and one [c1][c2 + 1] tile that carries stage 2's weights, tap by tap, into the input
-// gradient (lenet_conv_igrad_tiled), where they are read across ci.
-//
-// Validation, launch 1, grid (batch groups, D): as cfa_lenet.hip, a workgroup owns whole batches
-// and thread 0 sums a batch's losses in sample order. The chunk is the most samples (up to 4)
-// whose activations fit 64 KiB beside the batch's losses, or 1 sample under the device's limit; a
-// sample's arithmetic is its own, so the chunk moves no bit. Launch 2: lenet_finish_kernel.
-//
-// Gradient, launch 1, grid (sample groups, D): group g owns samples [g * kMaxGroup, ...) of the
-// batch whatever D, the CU count, skip or src are, and its slot workspace[d][g] (global memory)
-// holds its gradient sums: the slot starts at 0 and every sample adds its own sums to it, sample
-// by sample in order, each element by the one thread that owns it. A sample's weight-gradient
-// sums are lenet_conv_wgrad's and lenet_conv_bgrad's over that sample's rows alone, so the chunk
-// (up to 2 samples, as many as fit the device's LDS) moves no bit either: it only lets samples
-// share a phase, a barrier and a copy of a weight tile. Launch 2: lenet_grad_finish_kernel adds the
-// groups in order. No atomics; a device's row has the same bits alone or in a population.
-#include "cfa_lenet_graph.h"
+// The model stays out of LDS because 34 826 parameters (32 first-stage channels) are 136 KiB. At a
+// batch of 100 the validation chunk is 2 samples (62 816 bytes) with 32 channels and 3 (57 520
+// bytes) with 14; the gradient chunk is 1 sample (100 244 bytes) with 32 and 2 (132 700 bytes,
+// beyond the default 64 KiB) with 14, as many as fit the device's LDS.
+#include "cfa_lenet_global.h"
 
 namespace {
 
-constexpr int kMaxBlock = 512;     // 8 waves: the weights come from L2, and LDS leaves one or two workgroups a CU
-constexpr int kMaxEvalChunk = 4;   // most samples per pass through the forward phases
-constexpr int kMaxGradChunk = 2;   // most samples per pass through forward and backward
-constexpr int kMaxGroup = 8;       // samples per workgroup of the gradient kernel
-constexpr long long kLdsDefault = 65536;
-
-// LDS floats of the evaluation kernel for a chunk of n samples: their activations, a batch's losses.
-inline long long lenet_max_eval_lds(const LenetGeom& g, int n, int batch) {
-  return (long long)n * lenet_sample_floats(g) + batch;
-}
-
-// The chunk of the evaluation kernel (0: one sample's state does not fit `limit` bytes).
-inline int lenet_max_eval_chunk(const LenetGeom& g, int batch, long long limit) {
-  for (int n = kMaxEvalChunk; n >= 1; --n)
-    if (4 * lenet_max_eval_lds(g, n, batch) <= kLdsDefault) return n;
-  return 4 * lenet_max_eval_lds(g, 1, batch) <= limit ? 1 : 0;
-}
-
-// K: the kernel side at compile time, or 0; LOSS: the objective (CFA_LENET_LOSS_*).
-template <int K, int LOSS>
-__global__ __launch_bounds__(kMaxBlock) void lenet_max_eval_kernel(LenetArgs a, LenetGeom g, int chunk) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int dv = blockIdx.y;
-  if (a.skip && a.skip[dv]) return;  // the whole workgroup: the device has left its loop
-  const int tid = threadIdx.x, T = blockDim.x;
-  const int nx = g.side * g.side, n1 = g.p1 * g.p1 * g.c1;
-  float* xs = lds;                    // [chunk][side][side]
-  float* a1 = xs + chunk * nx;        // [chunk][p1][p1][c1]
-  float* a2 = a1 + chunk * n1;        // [chunk][flat]
-  float* zl = a2 + chunk * g.flat;    // [chunk][C]
-  float* loss = zl + chunk * g.C;     // [batch]
-  const float* m = a.models + (long long)dv * a.pitch;  // global: read through L2
-  const float* xd = a.x + (long long)dv * a.x_stride;
-  const int32_t* ld = a.labels + (long long)dv * a.label_stride;
-  for (int b = blockIdx.x; b < a.batches; b += gridDim.x) {
-    const long long first = (long long)b * a.batch;
-    for (int s0 = 0; s0 < a.batch; s0 += chunk) {
-      const int ns = min(chunk, a.batch - s0);
-      // the previous chunk's last read of xs was its first phase, three barriers ago
-      stage(xs, xd + (first + s0) * nx, ns * nx, tid, T);
-      __syncthreads();
-      lenet_conv_pool<K, LenetMaxPool>(a1, xs, m + g.oK1, m + g.ob1, ns, g.side, 1, g.c1, g.k, g.p1, tid, T);
-      __syncthreads();
-      lenet_conv_pool<K, LenetMaxPool>(a2, a1, m + g.oK2, m + g.ob2, ns, g.p1, g.c1, g.c2, g.k, g.p2, tid, T);
-      __syncthreads();
-      lenet_logits(zl, a2, m + g.oWd, m + g.obd, ns, g.flat, g.C, tid, T);
-      __syncthreads();
-      lenet_loss<LOSS>(loss + s0, zl, ld + first + s0, ns, g.C, tid, T);
-    }
-    __syncthreads();
-    if (tid == 0) {  // reduce_mean over the batch, fp32, in sample order
-      float c = 0.f;
-      for (int s = 0; s < a.batch; ++s) c += loss[s];
-      a.ws[(long long)dv * a.batches + b] = c / (float)a.batch;
-    }
-    // the next batch writes loss only after four more barriers
-  }
-}
-
-// LDS floats of the gradient kernel for a chunk of n samples: image, both pooled maps and their
-// gradients, logits and theirs, stage 2's gated map; the weight tile; a group's losses; the chunk's
-// labels; the decision bytes.
-inline long long lenet_max_grad_lds(const LenetGeom& g, int n) {
-  const long long n1 = (long long)g.p1 * g.p1 * g.c1, d2 = 4LL * g.p2 * g.p2 * g.c2;
-  const long long sample = (long long)g.side * g.side + 2 * n1 + 2 * g.flat + 2 * g.C + d2;
-  return n * sample + (long long)g.c1 * (g.c2 + 1) + kMaxGroup + n + (n * (n1 + g.flat) + 3) / 4;
-}
-
-// The chunk of the gradient kernel (0: one sample's state does not fit `limit` bytes).
-inline int lenet_max_grad_chunk(const LenetGeom& g, long long limit) {
-  for (int n = kMaxGradChunk; n >= 1; --n)
-    if (4 * lenet_max_grad_lds(g, n) <= limit) return n;
-  return 0;
-}
-
-template <int K, int LOSS>
-__global__ __launch_bounds__(kMaxBlock) void lenet_max_grad_kernel(LenetGradArgs a, LenetGeom g, int chunk) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int dv = blockIdx.y;
-  if (a.skip && a.skip[dv]) return;  // the whole workgroup
-  const int tid = threadIdx.x, T = blockDim.x;
-  const int P = (int)g.P, nx = g.side * g.side, n1 = g.p1 * g.p1 * g.c1, s2 = 2 * g.p2;
-  const int nd2 = s2 * s2 * g.c2;
-  float* xs = lds;                          // [chunk][side][side]
-  float* a1 = xs + chunk * nx;              // [chunk][p1][p1][c1]
-  float* da1 = a1 + chunk * n1;             // [chunk][p1][p1][c1]
-  float* a2 = da1 + chunk * n1;             // [chunk][flat]
-  float* da2 = a2 + chunk * g.flat;         // [chunk][flat] = [chunk][p2][p2][c2]
-  float* zl = da2 + chunk * g.flat;         // [chunk][C]
-  float* dzl = zl + chunk * g.C;            // [chunk][C]
-  float* dz2 = dzl + chunk * g.C;           // [chunk][2 p2][2 p2][c2]
-  float* tile = dz2 + chunk * nd2;          // [c1][c2 + 1]
-  float* loss = tile + g.c1 * (g.c2 + 1);   // [group]
-  int32_t* lab = reinterpret_cast<int32_t*>(loss + kMaxGroup);  // [chunk]
-  uint8_t* g1 = reinterpret_cast<uint8_t*>(lab + chunk);        // [chunk][p1][p1][c1]
-  uint8_t* g2 = g1 + chunk * n1;                                // [chunk][flat]
-  const int grp = blockIdx.x, begin = grp * kMaxGroup, count = min(kMaxGroup, a.batch - begin);
-  float* gs = a.ws + ((long long)dv * a.groups + grp) * (P + kMaxGroup);  // [P] the group's sums, then its losses
-  const int row = a.src ? a.src[dv] : dv;
-  if ((unsigned)row >= (unsigned)a.D) {  // the caller's error: nothing is read, the row becomes NaN
-    for (int i = tid; i < P + kMaxGroup; i += T) gs[i] = NAN;
-    return;
-  }
-  long long f0 = a.first ? a.first[dv] % a.Nt : 0;
-  if (f0 < 0) f0 += a.Nt;
-  const float* xd = a.x + (long long)dv * a.x_stride;
-  const int32_t* ld = a.labels + (long long)dv * a.label_stride;
-  const float* m = a.models + (long long)row * a.pitch;  // global: read through L2
-  for (int i = tid; i < P; i += T) gs[i] = 0.f;
-  for (int c0 = 0; c0 < count; c0 += chunk) {
-    const int ns = min(chunk, count - c0);
-    for (int j = 0; j < ns; ++j) {
-      const long long sample = (f0 + begin + c0 + j) % a.Nt;  // a batch past the set's end wraps
-      stage(xs + j * nx, xd + sample * nx, nx, tid, T);
-      if (tid == 0) lab[j] = ld[sample];
-    }
-    __syncthreads();  // also the sums' zeros, the first time: their owners read them from here on
-    lenet_conv_pool<K, LenetMaxPool>(a1, xs, m + g.oK1, m + g.ob1, ns, g.side, 1, g.c1, g.k, g.p1, tid, T, g1);
-    __syncthreads();
-    lenet_conv_pool<K, LenetMaxPool>(a2, a1, m + g.oK2, m + g.ob2, ns, g.p1, g.c1, g.c2, g.k, g.p2, tid, T, g2);
-    __syncthreads();
-    lenet_logits(zl, a2, m + g.oWd, m + g.obd, ns, g.flat, g.C, tid, T);
-    __syncthreads();
-    lenet_loss<LOSS>(loss + c0, zl, lab, ns, g.C, tid, T, dzl);
-    __syncthreads();
-    lenet_dense_backward(gs + g.oWd, gs + g.obd, da2, a2, dzl, m + g.oWd, ns, g.flat, g.C, tid, T);
-    __syncthreads();
-    lenet_store_gated(dz2, LenetMaxGated{g2, da2, g.p2, g.c2}, ns, tid, T);
-    __syncthreads();
-    for (int j = 0; j < ns; ++j) {  // a sample at a time: the sums do not depend on the chunk
-      const LenetStored d2{dz2 + j * nd2, s2, g.c2};
-      lenet_conv_wgrad<K>(gs + g.oK2, a1 + j * n1, d2, 1, g.p1, g.c1, g.c2, g.k, g.p2, tid, T);
-      lenet_conv_bgrad(gs + g.ob2, d2, 1, g.c2, g.p2, tid, T);
-    }
-    lenet_conv_igrad_tiled(da1, dz2, m + g.oK2, tile, ns, g.p1, g.c1, g.c2, g.k, g.p2, tid, T);
-    __syncthreads();
-    for (int j = 0; j < ns; ++j) {
-      const LenetMaxGated d1{g1 + j * n1, da1 + j * n1, g.p1, g.c1};
-      lenet_conv_wgrad<K>(gs + g.oK1, xs + j * nx, d1, 1, g.side, 1, g.c1, g.k, g.p1, tid, T);
-      lenet_conv_bgrad(gs + g.ob1, d1, 1, g.c1, g.p1, tid, T);
-    }
-    __syncthreads();  // the next chunk's images replace the ones just read
-  }
-  for (int i = tid; i < kMaxGroup; i += T) gs[P + i] = i < count ? loss[i] : 0.f;
-}
-
-inline int lenet_max_groups(int batch) { return (batch + kMaxGroup - 1) / kMaxGroup; }
-
-using LenetMaxEvalKernel = void (*)(LenetArgs, LenetGeom, int);
-using LenetMaxGradKernel = void (*)(LenetGradArgs, LenetGeom, int);
-
-// The kernel side the max-pool kernels are instantiated for: the drivers' 3, every other one 0.
-inline bool lenet_max_fast(const LenetGeom& g) { return g.k == 3; }
-
-inline LenetMaxEvalKernel lenet_max_eval_kernel_for(bool fast, int loss) {
-  if (loss == CFA_LENET_LOSS_HUBER)
-    return fast ? lenet_max_eval_kernel<3, CFA_LENET_LOSS_HUBER> : lenet_max_eval_kernel<0, CFA_LENET_LOSS_HUBER>;
-  return fast ? lenet_max_eval_kernel<3, CFA_LENET_LOSS_XENT> : lenet_max_eval_kernel<0, CFA_LENET_LOSS_XENT>;
-}
-
-inline LenetMaxGradKernel lenet_max_grad_kernel_for(bool fast, int loss) {
-  if (loss == CFA_LENET_LOSS_HUBER)
-    return fast ? lenet_max_grad_kernel<3, CFA_LENET_LOSS_HUBER> : lenet_max_grad_kernel<0, CFA_LENET_LOSS_HUBER>;
-  return fast ? lenet_max_grad_kernel<3, CFA_LENET_LOSS_XENT> : lenet_max_grad_kernel<0, CFA_LENET_LOSS_XENT>;
-}
+struct LenetMaxFamily {
+  using Pool = LenetMaxPool;
+  using Gated = LenetMaxGated;
+  static constexpr bool hidden = false;
+  static constexpr bool channels = false;  // x [side, side, 1]
+  static constexpr int side = 3;           // the drivers' kernel side
+  static constexpr bool grad_chunk_fills_device = true;
+  static constexpr const char* eval_name = "lenet_max_eval_kernel";
+  static constexpr const char* grad_name = "lenet_max_grad_kernel";
+};
 
 }  // namespace
 
-// Current device: raise the max-pool kernels' dynamic-LDS limit now (lenet_prepare_device), so
-// later launches (e.g. under hipGraph capture) need no attribute call.
-int lenet_max_prepare_device() {
-  const int lim = device_lds_max();
-  if (lim <= kLdsDefault) return CFA_OK;
-  for (int loss : {CFA_LENET_LOSS_XENT, CFA_LENET_LOSS_HUBER})
-    for (bool fast : {true, false}) {  // refused: launches stay within 64 KiB
-      (void)raise_lds_limit((const void*)lenet_max_eval_kernel_for(fast, loss), lim);
-      (void)raise_lds_limit((const void*)lenet_max_grad_kernel_for(fast, loss), lim);
-    }
-  return CFA_OK;
-}
+int lenet_max_prepare_device() { return lenet_global_prepare_device<LenetMaxFamily>(); }
 
 extern "C" size_t cfa_lenet_max_eval_workspace_bytes(int D, int batches) {
-  return D < 1 || batches < 1 ? 0 : (size_t)D * (size_t)batches * sizeof(float);
+  return lenet_global_eval_workspace_bytes(D, batches);
 }
 
 extern "C" int cfa_lenet_max_eval_loss_f32(const float* x, size_t x_dev_stride, const int32_t* labels,
@@ -228,33 +46,16 @@ extern "C" int cfa_lenet_max_eval_loss_f32(const float* x, size_t x_dev_stride, 
                                  models, pitch, D, batch, batches, target, ended, cost, cost_log, log_cap, epoch,
                                  workspace, workspace_bytes, cfa_lenet_max_eval_workspace_bytes(D, batches), loss, g))
     return rc;
-  // the kernel indexes the model and the LDS with ints
-  const LenetMaxEvalKernel kern = lenet_max_eval_kernel_for(lenet_max_fast(g), loss);
-  const long long limit = device_lds_max();
-  const int chunk = g.P > 0x7fffffffLL ? 0 : lenet_max_eval_chunk(g, batch, limit);
-  const long long need = chunk ? 4 * lenet_max_eval_lds(g, chunk, batch) : -1;
-  if (need < 0 || (need > kLdsDefault && !raise_lds_limit((const void*)kern, (int)limit)))
-    return fail(CFA_E_UNSUPPORTED, "%s: one sample's activations (%lld floats) and a batch of %d losses do not fit "
-                "one workgroup's LDS", fn, lenet_sample_floats(g), batch);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const LenetArgs a{x, labels, (long long)x_dev_stride, (long long)label_dev_stride, models, (long long)pitch,
-                    batch, batches, skip, static_cast<float*>(workspace)};
-  // about two workgroups per CU over all devices (what a 64 KiB chunk leaves room for), and every
-  // batch group the same number of batches (but the last)
-  const int gx = (int)shared_grid_x(batches, 2, D), per = (batches + gx - 1) / gx;
-  const dim3 grid((unsigned)((batches + per - 1) / per), (unsigned)D);
-  kern<<<grid, kMaxBlock, (size_t)need, st>>>(a, g, chunk);
-  if (int rc = check_launch("lenet_max_eval_kernel")) return rc;
-  const LenetFinish f{a.ws, D, batches, skip, target, ended, cost, cost_log, log_cap, epoch};
-  lenet_finish_kernel<<<1, kLenetFinishBlock, 0, st>>>(f);
-  return check_launch("lenet_finish_kernel");
+  return lenet_global_eval_launch<LenetMaxFamily>(fn, g, x, x_dev_stride, labels, label_dev_stride, models, pitch, D,
+                                                  batch, batches, skip, target, ended, cost, cost_log, log_cap, epoch,
+                                                  workspace, loss, stream);
 }
 
 extern "C" size_t cfa_lenet_max_grad_workspace_bytes(int D, int batch, int side, int kernel, int c1, int c2,
                                                      int classes) {
   LenetGeom g;
   if (D < 1 || batch < 1 || !lenet_geom(side, kernel, c1, c2, classes, g)) return 0;
-  return (size_t)D * (size_t)lenet_max_groups(batch) * (size_t)(g.P + kMaxGroup) * sizeof(float);
+  return lenet_global_grad_workspace_bytes(g, D, batch);
 }
 
 extern "C" int cfa_lenet_max_grad_loss_f32(const float* x, size_t x_dev_stride, const int32_t* labels,
@@ -268,26 +69,7 @@ extern "C" int cfa_lenet_max_grad_loss_f32(const float* x, size_t x_dev_stride, 
   if (int rc = lenet_grad_checks(fn, x, labels, x_dev_stride, label_dev_stride, Nt, side, kernel, c1, c2, classes, models,
                                  pitch, D, batch, grads, gpitch, workspace, loss_kind, g))
     return rc;
-  // the kernel indexes the model and the LDS with ints
-  const LenetMaxGradKernel kern = lenet_max_grad_kernel_for(lenet_max_fast(g), loss_kind);
-  const long long limit = device_lds_max();
-  const int chunk = g.P > 0x7fffffffLL ? 0 : lenet_max_grad_chunk(g, limit);
-  const long long need = chunk ? 4 * lenet_max_grad_lds(g, chunk) : -1;
-  if (need < 0 || (need > kLdsDefault && !raise_lds_limit((const void*)kern, (int)limit)))
-    return fail(CFA_E_UNSUPPORTED, "%s: one sample's activations and their gradients (%lld bytes) do not fit one "
-                "workgroup's LDS", fn, g.P > 0x7fffffffLL ? -1LL : 4 * lenet_max_grad_lds(g, 1));
-  const size_t ws_need = cfa_lenet_max_grad_workspace_bytes(D, batch, side, kernel, c1, c2, classes);
-  if (workspace_bytes < ws_need)
-    return fail(CFA_E_INVALID, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, ws_need);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int groups = lenet_max_groups(batch);
-  const LenetGradArgs a{x, labels, (long long)x_dev_stride, (long long)label_dev_stride, models, (long long)pitch,
-                        src, first, skip, Nt, batch, D, groups, static_cast<float*>(workspace)};
-  const dim3 grid((unsigned)groups, (unsigned)D);
-  kern<<<grid, kMaxBlock, (size_t)need, st>>>(a, g, chunk);
-  if (int rc = check_launch("lenet_max_grad_kernel")) return rc;
-  const LenetGradFinish f{a.ws, (int)g.P, groups, batch, skip, grads, (long long)gpitch, loss};
-  const dim3 fgrid((unsigned)((g.P + 1 + kLenetFinishBlock - 1) / kLenetFinishBlock), (unsigned)D);
-  lenet_grad_finish_kernel<kMaxGroup><<<fgrid, kLenetFinishBlock, 0, st>>>(f);
-  return check_launch("lenet_grad_finish_kernel");
+  return lenet_global_grad_launch<LenetMaxFamily>(fn, g, x, x_dev_stride, labels, label_dev_stride, Nt, models, pitch, D,
+                                                  src, first, batch, skip, grads, gpitch, loss, workspace,
+                                                  workspace_bytes, loss_kind, stream);
 }

@@ -27,7 +27,7 @@ no seed is shrunk, never the guard (no case needed it: `cifar`, with 4 064 pre-a
 three models and one batch of three samples, meets the rule at seed 1). test_lenet_hidden_host.py
 derives every seed again.
 
-`plan` restates the launch plan of cfa_lenet_hidden.hip from the geometry, the batch and the LDS
+`plan` restates the launch plan of cfa_lenet_global.h for this family from the geometry, the batch and the LDS
 limit alone, and `path` names the arithmetic that puts a case on the loop, tail or branch it exists for."""
 import numpy as np
 
@@ -65,7 +65,7 @@ EVAL_CASES = {
     "raised_lds": ((76, 3, 3, 1, 1, 2, 3), 2, 1, 3, 2),      # one sample's state above 64 KiB
 }
 
-# cfa_lenet_hidden.hip: kHidBlock, kHidEvalChunk, kHidGradChunk, kHidGroup
+# cfa_lenet_global.h: kGlobalBlock, kGlobalEvalChunk, kGlobalGradChunk, kGlobalGroup
 BLOCK, EVAL_CHUNK, GRAD_CHUNK, GROUP = 512, 4, 2, 8
 LDS_LIMIT = 160 * 1024
 # a geometry whose ONE-sample gradient state is beyond the device's LDS (from grad_lds_bytes, not by

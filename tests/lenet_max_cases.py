@@ -58,7 +58,7 @@ EVAL_CASES = {
     "raised_lds": ((90, 3, 4, 2, 3), 2, 1, 3, 3),      # one sample's activations above 64 KiB
 }
 
-# cfa_lenet_max.hip: kMaxBlock, kMaxEvalChunk, kMaxGradChunk, kMaxGroup
+# cfa_lenet_global.h: kGlobalBlock, kGlobalEvalChunk, kGlobalGradChunk, kGlobalGroup
 BLOCK, EVAL_CHUNK, GRAD_CHUNK, GROUP = 512, 4, 2, 8
 LDS_LIMIT = 160 * 1024
 
@@ -75,7 +75,7 @@ def eval_lds_bytes(geom, n, batch):
 
 
 def eval_chunk(geom, batch, lds_limit=LDS_LIMIT):
-    """lenet_max_eval_chunk: the most samples (up to 4) within 64 KiB, else 1 under the limit, else 0."""
+    """lenet_global_eval_chunk: the most samples (up to 4) within 64 KiB, else 1 under the limit, else 0."""
     for n in range(EVAL_CHUNK, 0, -1):
         if eval_lds_bytes(geom, n, batch) <= lc.LDS_DEFAULT:
             return n
@@ -83,7 +83,7 @@ def eval_chunk(geom, batch, lds_limit=LDS_LIMIT):
 
 
 def grad_lds_bytes(geom, n):
-    """lenet_max_grad_lds: n samples' activations and gradients, the weight tile, a group's losses,
+    """lenet_global_grad_lds: n samples' activations and gradients, the weight tile, a group's losses,
     the chunk's labels, the decision bytes."""
     side, k, c1, c2, classes = geom
     _, p1, _, p2 = lc.stages(geom)
